@@ -71,7 +71,16 @@ def parse():
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-api', action='store_true', help='skip the `api` objects (the reference\'s call spelling timed on the drop-in classes)')
     ap.add_argument('--cpu-full', action='store_true', help='gf2: time the CPU restatement on the full 4000 x 54000 matrix (~70 s) instead of citing the cached run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='product workload: after the timed steps, write what the last step computed (a fixed, seeded sample of the product rows of '
+                         'its last output slab, with their coefficients and pair indices) as DIR/<name>.npy, float64, at most 64 MB (rank 0)')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs is not None and args.workload != 'product':
+        ap.error('--dump-outputs is implemented for the product workload')
+    if args.dump_outputs is not None and (args.single_process or (args.gpus > 1 and 'WORLD_SIZE' not in os.environ)):
+        ap.error('--dump-outputs is implemented for one process per GPU (the default with --gpus 1 or under a launcher)')
     if os.environ.get('BENCH_CPU_FULL', '0') == '1':
         args.cpu_full = True                                      # the driver passes no flags: the environment switches the full-size CPU leg on
     # a millisecond-scale step needs more than three of them for a stable figure (clocks, allocator): mul_cleanup 20 + 3, gf2 10 + 2
@@ -136,9 +145,10 @@ def main():
         # this process (PyTorch wheels bundle their own HIP runtime; the product uses the system one)
         _lib.check(lib.symgpu_device_sync())
 
-    def timed_product(left_op, n_left, slab_rows, steps, warmup):
+    def timed_product(left_op, n_left, slab_rows, steps, warmup, last_slab=None):
         """warmup + `steps` timed steps of (all-gather when world > 1) + the product of `left_op` against the whole right operand in
-        output slabs of `slab_rows` outer rows -> (max-over-ranks seconds, launches of the row kernel, their summed HIP-event ms)."""
+        output slabs of `slab_rows` outer rows -> (max-over-ranks seconds, launches of the row kernel, their summed HIP-event ms).
+        `last_slab(op, o_begin)`, if given, sees the output slab of the last step's last launch before the ring is freed."""
         ring = [DeviceOp.alloc(slab_rows * n_left, wq, with_coeff=True) for _ in range(2)]
 
         def step():
@@ -160,6 +170,9 @@ def main():
         dt_ = time.perf_counter() - t0
         _lib.check(lib.symgpu_prof_enable(0, 0))
         nl_, ms_ = prof_read(_lib, 0)
+        if last_slab is not None:
+            n_slabs = (M + slab_rows - 1) // slab_rows
+            last_slab(ring[(n_slabs - 1) & 1], (n_slabs - 1) * slab_rows)
         for r in ring:
             r.free()
         return comm.max_over_ranks(dt_), nl_, ms_
@@ -173,7 +186,10 @@ def main():
         except parallel.CollectiveHang as exc:
             collective_hang(exc, args, rank, world)
         comm.verify_allgather(shard, right, M)
-    dt, n_launch, tot_ms = timed_product(left, Ni, slab, args.steps, args.warmup)
+    dump = None
+    if args.dump_outputs is not None and rank == 0:
+        dump = lambda op, o0: dump_product_slab(args.dump_outputs, op, o0, Ni, wq)
+    dt, n_launch, tot_ms = timed_product(left, Ni, slab, args.steps, args.warmup, last_slab=dump)
 
     pairs_per_step_rank = Ni * M
     value = world * pairs_per_step_rank * args.steps / dt
@@ -416,6 +432,33 @@ def summary_of(out):
     if errs:
         sm['failed_sections'] = errs
     return sm
+
+
+DUMP_SAMPLE_ROWS = 65536       # 1,000 qubits: 65,536 rows of 32 64-bit words -> 35 MB as float64 32-bit halves; fewer rows above 64 MB in all
+DUMP_SEED = 20251015
+
+
+def dump_product_slab(out_dir, op, o_begin, n_inner, wq):
+    """--dump-outputs for the product workload: what a caller of symgpu_mul_allpairs_dev receives for the last launch of the last step —
+    packed product rows and their coefficients — on a fixed, seeded sample of the slab's rows (gathered on the device, so that only the sample
+    is read back).  Row r of the slab is the pair (outer o_begin + r // n_inner, inner r % n_inner), pair index (o_begin + r // n_inner) * n_inner
+    + r % n_inner.  Files (float64, exact): product_pair_index (S,), product_rows_u32 (S, 4*wq) = each 64-bit word as its low and high 32-bit
+    halves, product_coeff (S, 2) = real, imag."""
+    from symmer_amd import kernels
+    T = op.n_terms
+    per_row = (4 * wq + 3) * 8
+    S = min(T, DUMP_SAMPLE_ROWS, (64 * 10**6) // per_row)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(T, size=S, replace=False)).astype(np.int64)
+    sample = kernels.op_gather(op, idx)
+    try:
+        rows, coeff = sample.download()
+    finally:
+        sample.free()
+    os.makedirs(out_dir, exist_ok=True)
+    words = rows.view('<u4').reshape(S, 4 * wq)
+    np.save(os.path.join(out_dir, 'product_pair_index.npy'), (o_begin * n_inner + idx).astype(np.float64))
+    np.save(os.path.join(out_dir, 'product_rows_u32.npy'), words.astype(np.float64))
+    np.save(os.path.join(out_dir, 'product_coeff.npy'), np.stack([coeff.real, coeff.imag], axis=1).astype(np.float64))
 
 
 def emit(out):

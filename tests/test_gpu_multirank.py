@@ -1,7 +1,7 @@
 """One process per GPU, world_size 2, on real hardware (`-m gpu`).
 
-* ``rccl``: needs two GPUs — RCCL all-gather over xGMI through ``Communicator.from_env`` + ``allgather_op`` (skipped on a
-  one-GPU box; the driver's 8-GPU scaling run exercises the same path through bench.py).
+* ``rccl``: RCCL all-gather over xGMI through ``Communicator.from_env`` + ``allgather_op``, two ranks on two GPUs; on a one-GPU box one
+  rank runs the same path (``SYMGPU_FORCE_COMM=1``: control plane, RCCL init, all-gather) — RCCL refuses two ranks on one device.
 * ``host-staged``: RCCL made unavailable on purpose (``SYMGPU_RCCL_DISABLE=1``) — the ranks must agree on the fallback
   before anybody enters ``ncclCommInitRank`` and gather through host memory; with one GPU both ranks share device 0.
 * bench.py's launch line with two ranks (torch.distributed.run's environment), reduced workload.
@@ -51,12 +51,13 @@ def _n_gpus():
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize('plane', ['rccl', 'host-staged'])
 def test_two_ranks_gather_and_blocks(plane):
-    if plane == 'rccl' and _n_gpus() < 2:
-        pytest.skip('RCCL needs one GPU per rank; this box has one')
     env = {'EXPECT_PLANE': plane}
+    world = 2
     if plane == 'host-staged':
         env['SYMGPU_RCCL_DISABLE'] = '1'
-    outs = _launch(['tests/_rank_worker.py'], 2, env)
+    elif _n_gpus() < 2:
+        world, env['SYMGPU_FORCE_COMM'] = 1, '1'                          # RCCL needs one GPU per rank: one rank through the same path
+    outs = _launch(['tests/_rank_worker.py'], world, env)
     for r, (rc, o, e) in enumerate(outs):
         assert rc == 0 and f'RANK_OK {r} {plane}' in o, f'rank {r}: rc={rc}\n{o}\n{e[-3000:]}'
 
@@ -114,33 +115,40 @@ def test_row_hash_collisions_are_caught_and_reseeded(worker):
     assert rc == 0 and 'WEAK_HASH_OK' in o, f'rc={rc}\n{o}\n{e[-3000:]}'
 
 
+# the GPU machines allow at most 6 processes with the GPU open at once, and this pytest process holds it already: 5 ranks is the largest
+# world size that fits (the 8-peer TCP control plane runs on the CPU: tests/test_parallel_gloo.py::test_world_size_8_tcp_control_plane)
+MAX_RANKS = 5
+
+
 @pytest.mark.timeout(900)
-def test_bench_eight_ranks_rank_arithmetic():
-    """bench.py at the driver's largest world size, reduced workloads (on a one-GPU box the eight ranks share the device and the
-    host-staged plane runs): shard bounds with a remainder (20,003 right terms / 40,003 adjacency terms over 8 ranks), the TCP
-    control plane with 8 peers, one JSON line from rank 0 only, aggregate pair counts."""
-    for argv, pairs in ((['bench.py', '--gpus', '8', '--steps', '1', '--warmup', '1', '--left-terms', '6000', '--right-terms', '20003', '--no-extras', '--no-cpu'],
-                         8 * 6000 * 20003),
-                        (['bench.py', '--gpus', '8', '--steps', '1', '--warmup', '1', '--workload', 'adjacency', '--adj-terms', '40003', '--adj-qubits', '300'],
+def test_bench_five_ranks_rank_arithmetic():
+    """bench.py at the largest world size the GPU machine allows, reduced workloads (on a one-GPU box the five ranks share the device and
+    the host-staged plane runs): shard bounds with a remainder (20,003 right terms / 40,003 adjacency terms over 5 ranks), the TCP
+    control plane with 5 peers, one JSON line from rank 0 only, aggregate pair counts."""
+    R = MAX_RANKS
+    for argv, pairs in ((['bench.py', '--gpus', str(R), '--steps', '1', '--warmup', '1', '--left-terms', '6000', '--right-terms', '20003', '--no-extras', '--no-cpu'],
+                         R * 6000 * 20003),
+                        (['bench.py', '--gpus', str(R), '--steps', '1', '--warmup', '1', '--workload', 'adjacency', '--adj-terms', '40003', '--adj-qubits', '300'],
                          40003 ** 2)):
-        outs = _launch(argv, 8, {}, timeout=800)
+        assert 20003 % R and 40003 % R                                    # the last rank's shard is the short one
+        outs = _launch(argv, R, {}, timeout=800)
         for r, (rc, o, e) in enumerate(outs):
             assert rc == 0, f'rank {r}: rc={rc}\n{o}\n{e[-3000:]}'
             assert (r == 0) == bool(o.strip()), (r, o)
         doc = json.loads(outs[0][1].strip().splitlines()[-1])
-        assert doc['n_gpus'] == 8 and doc['config']['pairs_per_step'] == pairs and doc['value'] > 0
-        if _n_gpus() < 8:
+        assert doc['n_gpus'] == R and doc['config']['pairs_per_step'] == pairs and doc['value'] > 0
+        if _n_gpus() < R:
             assert 'host-staged' in doc.get('degraded', '')
 
 
 # ---------------------------------------------------------------- one process, several devices (symmer_amd/multi.py) ----
 @pytest.mark.timeout(600)
-def test_single_process_device_group_on_all_devices():
+def test_single_process_device_group_on_all_devices(monkeypatch):
     """DeviceGroup over HipBackend on every visible device (symgpu_init_all, ncclCommInitAll, grouped all-gather, peer copies, one download
-    thread per device) against the C oracle.  Needs two devices; the pool's boxes have one (tests/test_gpu_resident.py runs the same code with
-    one device, tests/test_multi_device.py the block arithmetic for 8)."""
+    thread per device) against the C oracle.  With one device, SYMGPU_FORCE_COMM=1 keeps RCCL in the path (ncclCommInitAll with one
+    communicator, as `bench.py --single-process` on one device); tests/test_multi_device.py checks the block arithmetic for 8."""
     if _n_gpus() < 2:
-        pytest.skip('one process driving several devices needs several devices; this box has one')
+        monkeypatch.setenv('SYMGPU_FORCE_COMM', '1')
     import numpy as np
     from symmer_amd import multi, packing, _lib
     from oracle import oracle_c as oc

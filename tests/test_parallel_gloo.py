@@ -99,6 +99,23 @@ def test_world_size_3_tcp_control_plane():
         assert ok, f'rank {rank} failed: {err}'
 
 
+@pytest.mark.timeout(180)
+def test_world_size_8_tcp_control_plane():
+    """bench.py's control plane at the driver's largest world size: 8 peers (no GPU in the workers)."""
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_tcp_worker, args=(r, 8, port, q)) for r in range(8)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=150) for _ in procs]
+    for p in procs:
+        p.join(timeout=30)
+    assert sorted(r for r, _, _ in res) == list(range(8))
+    for rank, ok, err in res:
+        assert ok, f'rank {rank} failed: {err}'
+
+
 @pytest.mark.timeout(120)
 def test_tcp_control_plane_survives_an_occupied_port():
     """The first candidate port is held by an unrelated (silent) listener: rank 0 must move on, the peers must find it."""
