@@ -66,7 +66,7 @@ struct Context {
     u64 *hash_tab = nullptr;       // device, [8][256][2]
     u64 hash_seed = 0;
     std::vector<u64> host_hash_tab;  // host copy of hash_tab (to hash single rows, e.g. a rotation's Q, with the SAME device's tables)
-    u64 *xs_pow = nullptr;         // device, [32][64]: columns of M^(2^j), M = the hash's xorshift step (k_hash_rows_long, cleanup.hip)
+    u64 *xs_pow = nullptr;         // device, [32][64]: columns of M^(2^j), M = the hash's xorshift step (k_hash_rows_long, cleanup_hash.hip)
     // rotation hash join (rotate.hip): persistent open-addressing table of [tag 32 | generation 10 | row index + 1 : 22] entries.
     // An entry of another generation is empty, so the table is cleared once per 1023 rotations instead of once per rotation.
     u64 *rot_table = nullptr;
@@ -250,13 +250,13 @@ __device__ __forceinline__ void pair_coefficient(double ar, double ai, double br
     apply_phase(re, im, e, ore, oim);
 }
 
-// packed pair key of the fused product + cleanup: [hash: 64-F bits][e: 2][o: bo][i: bi], F = bi + bo + 2 (cleanup.hip)
+// packed pair key of the fused product + cleanup: [hash: 64-F bits][e: 2][o: bo][i: bi], F = bi + bo + 2 (cleanup_common.h)
 struct PairKeyArgs {
     const u64 *hI, *hO;     // per-operand row hashes
     u64 *keys;              // [No*Ni] out, index o*Ni + i  (squared mode: compacted, see below)
     int bi, bo;
     i64 o_base;             // absolute index of the launch's first outer row
-    // squared mode (P * P, cleanup.hip): only the pairs with i >= o get a key (the twin (o, i) of an off-diagonal pair is the
+    // squared mode (P * P, cleanup_driver.hip): only the pairs with i >= o get a key (the twin (o, i) of an off-diagonal pair is the
     // same row with the same or the opposite coefficient), compacted in pair-index order: slot(o, i) = o*Ni - o(o-1)/2 + (i - o)
     int squared = 0;
     // round 6, ebytes != null: instead of the 8-byte key ONE byte per pair at the key's index, e | (i == o) << 2 — all that the marking of
@@ -276,16 +276,22 @@ int wide_commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t 
 int wide_mul_coeff_dev(const u64 *inner, const double *ci, i64 Ni, const u64 *outer, const double *co, i64 o_begin, i64 o_end, int Wq,
                        int inner_is_left, double *out_coeff, const PairKeyArgs *keys);
 
-// cleanup.hip
+// cleanup_hash.hip, cleanup_driver.hip
 extern i64 g_hash_reseeds;                                      // row-hash collisions that forced a reseed (never seen outside the tests)
 int ensure_hash_tables(u64 seed);
 int hash_rows(const u64 *rows, i64 T, int W, u64 *out1);       // h1 of every row (current tables)
 u64 host_row_hash(const u64 *row, int W);                       // the same hash on the host
-int cleanup_core(const u64 *rows, const double *coeff, i64 T, int W,          // plain mode (pair mode if inner != null)
-                 const u64 *inner, i64 Ni, const u64 *outer, i64 No,
-                 double thr, int use_thr, symgpu_op_t *out, int Wq_out,
-                 const double *ci = nullptr, const double *co = nullptr, int inner_is_left = 1,    // pair mode: operand coefficients
-                 bool want_first = false);                                                          // the result carries symgpu_op_s::first
+// product + cleanup: term t = o * Ni + i is inner[i] ^ outer[o] with coefficient ci[i] * co[o] * i^e (product.hip)
+struct PairOperands {
+    const u64 *inner = nullptr, *outer = nullptr;
+    const double *ci = nullptr, *co = nullptr;
+    i64 Ni = 0, No = 0;
+    int W = 0, Wq_out = 0;                                      // words of an operand row (2 * Wq) / chunks of a result row
+    int inner_is_left = 1;
+};
+// *out is a fresh operator with the cleaned result; want_first: it carries symgpu_op_s::first
+int cleanup_rows(const u64 *rows, const double *coeff, i64 T, int W, double thr, int use_thr, symgpu_op_t *out, int Wq_out, bool want_first = false);
+int cleanup_pairs(const PairOperands &p, double thr, int use_thr, symgpu_op_t *out, bool want_first = false);
 
 // pair_dups.hip — the pairs of a product whose 64-bit key another pair shares, found without sorting the keys
 bool pair_dups_fits(i64 Ni, i64 No, bool squared, i64 Tk, int *B_out, int *sb_out = nullptr);      // host-side: would pair_dups_dev take this product?

@@ -37,7 +37,7 @@ static Context g_ctxs[SYMGPU_MAX_DEVICES];
 static int g_default_dev = -1;                    // the first device initialised in this process
 static thread_local int t_cur_dev = -1;           // this thread's selection (-1: the default)
 static thread_local int t_bound_dev = -1;         // the device hipSetDevice was last called with on this thread
-i64 g_counters[16] = {0};   // symgpu_debug_counter 1..10 (0 is g_hash_reseeds, cleanup.hip)
+i64 g_counters[16] = {0};   // symgpu_debug_counter 1..10 (0 is g_hash_reseeds, cleanup_hash.hip)
 static int cur_index() { return t_cur_dev >= 0 ? t_cur_dev : (g_default_dev >= 0 ? g_default_dev : 0); }
 Context &ctx() { return g_ctxs[cur_index()]; }
 Context *ctx_of_device(int device) { return device >= 0 && device < SYMGPU_MAX_DEVICES ? &g_ctxs[device] : nullptr; }

@@ -2,7 +2,7 @@
 //
 // A rank owns the pairs whose product row falls in its GF(2)-linear class: a union of full sub-products (inner rows of class a) x (outer
 // rows whose class maps to the rank).  Per sub-product: symgpu_op_gather picks the sub-operands out of the complete operands,
-// symgpu_mul_cleanup_indexed_dev (cleanup.hip) multiplies and cleans them and keeps the first pair (o << 32 | i, sub-operand numbering) of
+// symgpu_mul_cleanup_indexed_dev (cleanup_driver.hip) multiplies and cleans them and keeps the first pair (o << 32 | i, sub-operand numbering) of
 // every output row, symgpu_part_global_index turns that into the reference's pair index o_global * Ni + i_global (base.py:783-792).
 // symgpu_merge_indexed_dev then concatenates the parts, orders them by pair index (radix sort of the 8-byte indices, rows gathered once),
 // merges the rows that several parts share (first-occurrence cleanup: duplicates across the sub-products of one rank) and applies the
@@ -182,7 +182,7 @@ int symgpu_merge_indexed_dev(const symgpu_op_t *parts, int n_parts, int key_bits
     }
     // rows that several parts share merge at their first occurrence = smallest pair index; sums in pair order of the parts' partial sums
     symgpu_op_t res = nullptr;
-    rc = cleanup_core(sorted->rows, sorted->coeff, total, W, nullptr, 0, nullptr, 0, thr, use_thr, &res, Wq, nullptr, nullptr, 1, true);
+    rc = cleanup_rows(sorted->rows, sorted->coeff, total, W, thr, use_thr, &res, Wq, true);
     if (rc == SYMGPU_OK && res->T > 0) {
         // res->first[t] = position in the sorted concatenation -> its pair index
         Scratch g;

@@ -211,7 +211,7 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
                        sign.as<unsigned char>(), d_src.as<u32>(), W_out, t_rows.as<u64>(), t_coeff.as<double>());
     KERNEL_CHECK();
     // equal projected terms merge (the reference's .cleanup() at projection/base.py:82)
-    return cleanup_core(t_rows.as<u64>(), t_coeff.as<double>(), n_s, W_out, nullptr, 0, nullptr, 0, thr, use_thr, out, Wq_out);
+    return cleanup_rows(t_rows.as<u64>(), t_coeff.as<double>(), n_s, W_out, thr, use_thr, out, Wq_out);
 }
 
 int symgpu_noncontextual_dev(symgpu_op_t op, int *is_noncontextual) {
@@ -248,7 +248,7 @@ int symgpu_noncontextual_dev(symgpu_op_t op, int *is_noncontextual) {
     // non-universal terms into cliques iff no column sits in two of them: every column is in at least one (a term commutes with itself),
     // so iff the set bits of the unique rows add up to the number of columns
     symgpu_op_t uniq = nullptr;
-    SG_TRY(cleanup_core(c_rows.as<u64>(), c_coeff.as<double>(), n_nu, W2, nullptr, 0, nullptr, 0, 0.0, 0, &uniq, W2 / 2));
+    SG_TRY(cleanup_rows(c_rows.as<u64>(), c_coeff.as<double>(), n_nu, W2, 0.0, 0, &uniq, W2 / 2));
     uint64_t ones = 0;
     const int rc = symgpu_op_popcount(uniq, &ones);
     symgpu_op_free(uniq);

@@ -8,7 +8,7 @@
 //           (e = (3(Y_P+Y_Q) + Y_out + 2|x_P & z_Q|) mod 4), G lanes per row, xor/popcount + shuffles.
 // scan    : positions of anticommuting rows (exclusive scan of flags).
 // build   : non-Clifford: stack [commuting | cos * anticommuting | (-i sin) i^e * (anticommuting ^ Q)] in the
-//           reference's order (base.py:1158-1161), then first-occurrence cleanup (cleanup.hip) merges P^Q
+//           reference's order (base.py:1158-1161), then first-occurrence cleanup (cleanup_driver.hip) merges P^Q
 //           partners; Clifford (angle = k*pi/2): [rotated anticommuting | commuting], no merge (base.py:1139-1154);
 //           odd k: row ^ Q with c * i^e * (-i), k in {2,3}: negated (k is NOT reduced mod 4, base.py:1148).
 // Equivalent to the reference's three intermediate cleanups when the input has no duplicate rows
@@ -25,7 +25,7 @@ namespace symgpu {
 
 
 // flags[t] = 1 iff row t anticommutes with q;  ph[t] = phase exponent e of (row_t * q).
-// HASH: also the linear row hash h1 of cleanup.hip (same tables, same per-lane Horner) for the hash-join fast path.
+// HASH: also the linear row hash h1 of cleanup_hash.hip (same tables, same per-lane Horner) for the hash-join fast path.
 __device__ __forceinline__ u64 rot_rotl64(u64 x, int r) { r &= 63; return r ? ((x << r) | (x >> (64 - r))) : x; }
 
 // insert row t (hash h) — duplicates (same tag AND same words) raise the flag; one lane per row
@@ -1190,7 +1190,7 @@ int symgpu_rotate_single_dev(symgpu_op_t in, const uint64_t *q_row_host, double 
         // (anticom_self * Q) of base.py:1143 = cleanup of the rotated rows: duplicates merged in input order, |sum| > thr kept
         // (the exact factors -i / -1 commute with the IEEE sums); then the commuting rows, untouched (base.py:1151-1154)
         symgpu_op_t merged = nullptr;
-        int rc = cleanup_core(stack->rows, stack->coeff, n_sel, W, nullptr, 0, nullptr, 0, thr, 1, &merged, Wq);
+        int rc = cleanup_rows(stack->rows, stack->coeff, n_sel, W, thr, 1, &merged, Wq);
         if (rc != SYMGPU_OK) { symgpu_op_free(stack); return rc; }
         symgpu_op_t res = nullptr;
         rc = symgpu_op_alloc(merged->T + n_comm > 0 ? merged->T + n_comm : 1, Wq, 1, &res);
@@ -1216,7 +1216,7 @@ int symgpu_rotate_single_dev(symgpu_op_t in, const uint64_t *q_row_host, double 
         return SYMGPU_OK;
     }
     symgpu_op_t res = nullptr;
-    int rc = cleanup_core(stack->rows, stack->coeff, n_stack, W, nullptr, 0, nullptr, 0, thr, 1, &res, Wq);
+    int rc = cleanup_rows(stack->rows, stack->coeff, n_stack, W, thr, 1, &res, Wq);
     symgpu_op_free(stack);
     if (rc != SYMGPU_OK) return rc;
     *out = res;

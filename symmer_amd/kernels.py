@@ -295,7 +295,7 @@ def mul_cleanup_handles(a, b, inner_is_left=True, zero_threshold=1e-15, max_pair
 
 def mul_cleanup(inner, ci, outer, co, inner_is_left=True, zero_threshold=1e-15, max_pairs=None):
     """Host arrays in, host arrays out around :func:`mul_cleanup_handles` (``outer is inner``: one device operand serves both factors,
-    which lets the library sort half of the pairs, cleanup.hip)."""
+    which lets the library sort half of the pairs, cleanup_driver.hip)."""
     same = outer is inner and co is ci
     inner, outer, ci, co = _rows(inner), _rows(outer), _coeff(ci), _coeff(co)
     assert inner.shape[1] == outer.shape[1]

@@ -317,7 +317,7 @@ def test_one_launch_rotation_with_the_rows_left_in_memory(n, N, monkeypatch):
 
 @pytest.mark.parametrize('shape', ['squared 3000', 'general 2500x2000', 'general 2000x2500'])
 def test_product_cleanup_over_the_lazy_gate_against_the_c_oracle(shape):
-    """Product + cleanup with more than 2^22 keys on the DEFAULT path (the lazy flow of cleanup.hip switches on there by itself;
+    """Product + cleanup with more than 2^22 keys on the DEFAULT path (the lazy flow of cleanup_driver.hip switches on there by itself;
     round 3 only compared it with the forced gate or with the round-2 flow), 100 qubits, against the C oracle (utils.py:230-279):
     a squared operator (4.5e6 keys of its 9e6 pairs) and general products in both operand orders (5e6 keys), dyadic coefficients:
     rows, first-occurrence order and coefficients bit for bit."""

@@ -15,9 +15,11 @@ case $wl in
 esac
 out=gpurun_out/${tag}_$wl; rm -rf $out; mkdir -p $out
 cmd="bench.py --workload $wl --steps 2 --warmup 1 --no-extras --no-cpu --no-api"
-timeout 900 rocprofv3 --pmc WRITE_SIZE -d $out/w -o w -- python3 $cmd > $out/w.log 2>&1
-timeout 900 rocprofv3 --pmc FETCH_SIZE -d $out/r -o r -- python3 $cmd > $out/r.log 2>&1
-timeout 900 rocprofv3 --kernel-trace --stats -d $out/t -o t -- python3 $cmd > $out/${tag}_${short}_n1.json 2> $out/t.log
+# each GPU run under its own time limit; the first one that fails ends the script (nothing more is started on the GPU after a fault)
+timeout -k 10 900 rocprofv3 --pmc WRITE_SIZE -d $out/w -o w -- python3 $cmd > $out/w.log 2>&1 &&
+timeout -k 10 900 rocprofv3 --pmc FETCH_SIZE -d $out/r -o r -- python3 $cmd > $out/r.log 2>&1 &&
+timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $out/t -o t -- python3 $cmd > $out/${tag}_${short}_n1.json 2> $out/t.log ||
+  { rc=$?; echo "rocprofv3 step failed (exit $rc); see $out/*.log"; exit $rc; }
 python3 profiles/summarize_rocpd.py $out/t/t_results.db | head -24 > $out/${tag}_${short}_kernel_trace.txt
 python3 profiles/summarize_rocpd.py --pmc $out/w/w_results.db --pmc $out/r/r_results.db | grep -E "^#|counter|k_emit|k_rot_res|k_sweep|k_heads|k_rs_|k_commutes|k_select|k_mul_coeff|k_mark|k_fixup|k_find" > $out/${tag}_${short}_pmc.txt
 python3 - "$out" "$tag" "$wl" "$short" "$like" $srcs <<'PY'
