@@ -25,7 +25,7 @@ __global__ void k_pair_keys(const u64 *__restrict__ hI, i64 Ni, const u64 *__res
 // PACKED: keys[s] is the packed key of index s (pair index, or slot of a squared operator); otherwise coeff[s].
 // One workgroup per tile of SORT_TILE indices (= the radix sort's tile).  hist != null (packed keys): the same pass forms the digit
 // histograms of the sort's first pass, which reads these very keys in this very order (one HBM pass over the keys less).
-// smallest max(|re|, |im|) over the terms of an operand (0 if a component is not a number), as the bit pattern of a non-negative double
+// smallest max(|re|, |im|) over the terms of an operand (0 if a component is not finite), as the bit pattern of a non-negative double
 // (ordered like the unsigned integer): *slot starts as all ones
 __global__ __launch_bounds__(1024) void k_coeff_floor(const double *__restrict__ c0, i64 n0, const double *__restrict__ c1, i64 n1,
                                                       unsigned long long *__restrict__ slot0, int one_block) {
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(1024) void k_coeff_floor(const double *__restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const double a = fabs(v[k].x), b = fabs(v[k].y);
-            const double mx = (a == a && b == b) ? (a > b ? a : b) : 0.0;
+            const double mx = (a <= __DBL_MAX__ && b <= __DBL_MAX__) ? (a > b ? a : b) : 0.0;
             m = mx < m ? mx : m;
         }
     }
@@ -55,7 +55,9 @@ __global__ __launch_bounds__(1024) void k_coeff_floor(const double *__restrict__
 // floor_i / floor_o (packed keys; null: none): k_coeff_floor of the two operands.  |c_i c_o| >= floor_i * floor_o, the larger component of
 // the computed product is at least 0.7 of that, so when half of it exceeds thr every pair of non-zero weight is kept WHATEVER its
 // coefficient: the two table gathers, the complex product and the comparison (50 of the kernel's 70 instructions per key) are skipped
-// — the decision is the same, it is just not computed (cfg3: 0.19 -> see DESIGN 3.3).
+// — the decision is the same, it is just not computed (cfg3: 0.19 -> see DESIGN 3.3).  It needs finite operands (a product of finite
+// factors never has two NaN components, and an inf component is kept) and a normal floor product (no subnormal rounding eats the 0.7).
+__device__ __forceinline__ bool floors_clear(double fi, double fo, double thr) { return 0.5 * fi * fo > thr && fi * fo > 0x1p-1000; }
 template <bool PACKED>
 __global__ __launch_bounds__(256) void k_mark_singles(const u64 *__restrict__ keys, const double *__restrict__ coeff, i64 space, PackedLayout L,
                                                        const double *__restrict__ ci, const double *__restrict__ co, int squared, double thr, int use_thr,
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(256) void k_mark_singles(const u64 *__restrict__ ke
                                                        const double *__restrict__ floor_o) {
     __shared__ u32 s_h[256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool all_kept = PACKED && (!use_thr || (floor_i && floor_o && 0.5 * floor_i[0] * floor_o[0] > thr));   // block-uniform
+    const bool all_kept = PACKED && (!use_thr || (floor_i && floor_o && floors_clear(floor_i[0], floor_o[0], thr)));   // block-uniform
     if (hist) { s_h[threadIdx.x] = 0; __syncthreads(); }
     const i64 tile_base = (i64)blockIdx.x * SORT_TILE;
 #pragma unroll 1
@@ -117,10 +119,8 @@ __global__ __launch_bounds__(256) void k_mark_singles(const u64 *__restrict__ ke
                     else { cx = __dadd_rn(cx, cx); cy = __dadd_rn(cy, cy); }
                 }
             }
-            // strict |c| > thr: a component that alone exceeds thr decides it (hypot is faithfully rounded and >= either component)
-            // (and an exact zero — every anticommuting pair of a squared operator — needs no hypot either)
-            const bool zero = cx == 0.0 && cy == 0.0;
-            keep = valid && (!use_thr || (zero ? 0.0 > thr : (fabs(cx) > thr || fabs(cy) > thr || hypot(__dadd_rn(0.0, cx), __dadd_rn(0.0, cy)) > thr)));
+            // strict |c| > thr as NumPy decides it (common.h)
+            keep = valid && (!use_thr || above_thr(cx, cy, thr));
             }
             const u64 mk = __ballot(keep);
             const i64 chunk = (g0 + 64 * j) / 64;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void k_mark_bytes(const u32x4 *__restrict__ eb
                                                      const double *__restrict__ co, int squared, double thr, int use_thr, unsigned short *__restrict__ mark16,
                                                      unsigned short *__restrict__ lo16, unsigned short *__restrict__ hi16, const double *__restrict__ floor_i,
                                                      const double *__restrict__ floor_o) {
-    const bool all_kept = !use_thr || (floor_i && floor_o && 0.5 * floor_i[0] * floor_o[0] > thr);     // uniform
+    const bool all_kept = !use_thr || (floor_i && floor_o && floors_clear(floor_i[0], floor_o[0], thr));     // uniform
     const bool drop_rule = use_thr && squared && !(0.0 > thr);           // the anticommuting off-diagonal pairs of a squared operator are exact zeros
     for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < n_groups; g += (i64)gridDim.x * blockDim.x) {
         const i64 p0 = g * 16;
@@ -192,8 +192,7 @@ __global__ __launch_bounds__(256) void k_mark_bytes(const u32x4 *__restrict__ eb
                     if (e & 1) { cx = 0.0; cy = 0.0; }
                     else { cx = __dadd_rn(cx, cx); cy = __dadd_rn(cy, cy); }
                 }
-                const bool zero = cx == 0.0 && cy == 0.0;
-                const bool kp = !use_thr || (zero ? 0.0 > thr : (fabs(cx) > thr || fabs(cy) > thr || hypot(__dadd_rn(0.0, cx), __dadd_rn(0.0, cy)) > thr));
+                const bool kp = !use_thr || above_thr(cx, cy, thr);
                 keep |= (kp ? 1u : 0u) << k;
             }
         }

@@ -151,7 +151,7 @@ __global__ void k_zero_close(const u64 *__restrict__ keys, const double *__restr
     if (diag_seq && len == (u64)Ni && *offdiag == 0u) { re = diag_seq[0]; im = diag_seq[1]; }
     *zero_len = (u32)len;
     if (len == 0) return;
-    if (use_thr && !(hypot(re, im) > thr)) return;
+    if (use_thr && !above_thr(re, im, thr)) return;
     const u64 k0 = keys[0];                                           // stable sort: the segment's smallest pair index
     const u32 first = tri_slot(L.o(k0), L.i(k0), Ni);
     atomicOr(&markbits[first >> 5], 1u << (first & 31u));
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void k_heads_sums(const u64 *__restrict__ keys
     const bool lazy = patchbits != nullptr;
     auto close = [&](u32 first, double re, double im, bool multi) {   // strict threshold, bitmap, sum filed under the first index
         if (lazy && !multi) return;                                   // a single: decided by k_mark_singles, rebuilt by k_emit_meta
-        if (use_thr && !(hypot(re, im) > thr)) {
+        if (use_thr && !above_thr(re, im, thr)) {
             if (lazy) atomicAnd(&markbits[first >> 5], ~(1u << (first & 31u)));
             return;
         }

@@ -243,6 +243,25 @@ __device__ __forceinline__ void apply_phase(double re, double im, int e, double 
     ore = neg_a ? -a : a;
     oim = neg_b ? -b : b;
 }
+// |re + i im| as NumPy's complex abs forms it (its SIMD loop, x86-64 with FMA): an infinite component gives inf, else a NaN gives NaN,
+// else max * sqrt(fma(r, r, 1)) with r = min / max, every step correctly rounded.  It is not libm's hypot: the two differ by an ulp
+// on about one coefficient in ten, and an ulp at |c| ~ thr decides whether a row is kept (tests/test_gpu_coeff_edges.py).
+__device__ __forceinline__ double numpy_cabs(double re, double im) {
+    const double a = fabs(re), b = fabs(im);
+    if (a == __builtin_inf() || b == __builtin_inf()) return __builtin_inf();
+    if (a != a || b != b) return __builtin_nan("");
+    const double big = a > b ? a : b, small = a > b ? b : a;
+    if (big == 0.0) return 0.0;
+    const double r = __ddiv_rn(small, big);
+    return __dmul_rn(__dsqrt_rn(__fma_rn(r, r, 1.0)), big);
+}
+// the keep rule of every cleanup and rotation: NumPy's np.abs(c) > thr (strict; NaN is dropped).  A component above thr decides it
+// without the division when the other component is a number (|c| >= either component); with a NaN beside it only an inf keeps the term.
+__device__ __forceinline__ bool above_thr(double re, double im, double thr) {
+    const double a = fabs(re), b = fabs(im);
+    if ((a > thr && b == b) || (b > thr && a == a)) return true;
+    return numpy_cabs(a, b) > thr;
+}
 // plain IEEE complex product (no FMA contraction: matches numpy for exactly representable inputs) times i^e
 __device__ __forceinline__ void pair_coefficient(double ar, double ai, double br, double bi, int e, double &ore, double &oim) {
     const double re = __dsub_rn(__dmul_rn(ar, br), __dmul_rn(ai, bi));

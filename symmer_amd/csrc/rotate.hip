@@ -199,7 +199,7 @@ __global__ void k_rot_keepflags(const u32 *__restrict__ anti, const double *__re
                                 u32 *__restrict__ keep) {
     for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (i64)gridDim.x * blockDim.x) {
         u32 k = anti[t];
-        if (k && drop_small && !(hypot(coeff[2 * t], coeff[2 * t + 1]) > thr)) k = 0;
+        if (k && drop_small && !above_thr(coeff[2 * t], coeff[2 * t + 1], thr)) k = 0;
         keep[t] = k;
     }
 }
@@ -330,25 +330,26 @@ __global__ __launch_bounds__(1024) void k_rotf_match2(const u64 *__restrict__ ro
             }
         }
         const double re = coeff[2 * t], im = coeff[2 * t + 1];
+        // every coefficient leaves as 0 + c, as the reference's cleanup forms it (a zero component is +0)
         if (!is_anti) {
-            selfc[2 * t] = re; selfc[2 * t + 1] = im;
-            if (hypot(re, im) > thr) c = 1;
+            selfc[2 * t] = __dadd_rn(0.0, re); selfc[2 * t + 1] = __dadd_rn(0.0, im);
+            if (above_thr(re, im, thr)) c = 1;
         } else {
             double sr = __dmul_rn(re, cos_t), si = __dmul_rn(im, cos_t);
             if (partner >= 0) {                                  // merge: (0 + cos*c_t) + (-i sin) i^{e_p} c_p, in that order
                 double pr, pi;
                 phase_mul(coeff[2 * partner], coeff[2 * partner + 1], ph[partner], pr, pi);
-                sr = __dadd_rn(sr, __dmul_rn(pi, sin_t));
-                si = __dadd_rn(si, -__dmul_rn(pr, sin_t));
+                sr = __dadd_rn(__dadd_rn(0.0, sr), __dmul_rn(pi, sin_t));
+                si = __dadd_rn(__dadd_rn(0.0, si), -__dmul_rn(pr, sin_t));
             } else {                                             // its product row is new
                 double pr, pi;
                 phase_mul(re, im, ph[t], pr, pi);
                 const double nr = __dmul_rn(pi, sin_t), ni = -__dmul_rn(pr, sin_t);
-                prodc[2 * t] = nr; prodc[2 * t + 1] = ni;
-                if (hypot(nr, ni) > thr) c |= 4;
+                prodc[2 * t] = __dadd_rn(0.0, nr); prodc[2 * t + 1] = __dadd_rn(0.0, ni);
+                if (above_thr(nr, ni, thr)) c |= 4;
             }
-            selfc[2 * t] = sr; selfc[2 * t + 1] = si;
-            if (hypot(sr, si) > thr) c |= 2;
+            selfc[2 * t] = __dadd_rn(0.0, sr); selfc[2 * t + 1] = __dadd_rn(0.0, si);
+            if (above_thr(sr, si, thr)) c |= 2;
         }
         cls[t] = c;
     }
@@ -501,7 +502,7 @@ __global__ __launch_bounds__(1024) void k_rotc_classify(const u32 *__restrict__ 
             c = 1;
             selfc[2 * t] = re; selfc[2 * t + 1] = im;
         } else if (k & 1) {
-            if (hypot(re, im) > thr) {
+            if (above_thr(re, im, thr)) {
                 double x, y;
                 phase_mul(re, im, ph[t], x, y);
                 double pr = y, pi = -x;

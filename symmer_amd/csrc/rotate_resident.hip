@@ -170,14 +170,11 @@ __device__ __forceinline__ void res_leave(const ResArgs &a) {
     }
 }
 
+// 0 + c, as the reference's cleanup forms every coefficient of a non-Clifford rotation (a zero component leaves as +0)
+__device__ __forceinline__ f64x2 plus_zero(f64x2 c) { return f64x2{__dadd_rn(0.0, c.x), __dadd_rn(0.0, c.y)}; }
 // rows leave with non-temporal stores; write-through (sc0 sc1) stores measured the same kernel duration (27.5 us)
 __device__ __forceinline__ void row_store(u32x4 v, u32x4 *p) { __builtin_nontemporal_store(v, p); }
 #define RES_STAMP(i) do { if (a.trace && tid == 0) a.trace[(size_t)w * 16 + (i)] = wall_clock64(); } while (0)
-
-// |c| > thr as NumPy's abs(complex) decides it (hypot), without the hypot for every coefficient that has a component above thr
-__device__ __forceinline__ bool res_keep(double re, double im, double thr) {
-    return (fabs(re) > thr || fabs(im) > thr) ? true : hypot(re, im) > thr;
-}
 
 // flag and the two phase exponents of a row from its counts (rotate.hip: k_rot_analyze): bit 0 = anticommutes with Q, bits 1-2 = the
 // exponent e of P * Q, bits 3-4 = the exponent e' of (P ^ Q) * Q, i.e. the e of the row's partner
@@ -350,7 +347,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
             u32 ps = 0;
             if (!(info & 1)) {
                 const f64x2 c = s_coef[r];
-                if (res_keep(c.x, c.y, a.thr)) { cls = CL_C; ++nC; }
+                if (above_thr(c.x, c.y, a.thr)) { cls = CL_C; ++nC; }
             } else if (WQ > 0 && (s_cls[r] & CL_CLAIMED)) {
                 cls = CL_CLAIMED; ps = s_ps[r];                                // claimed by the probe issued from the load loop
             } else {
@@ -441,15 +438,15 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
             if (part >= 0) {                                                   // (0 + cos c_t) + (-i sin) i^{e'} c_p, in that order
                 const f64x2 cp = coeff2[part];
                 phase_mul(cp.x, cp.y, (info >> 3) & 3, pr, pi);
-                sr = __dadd_rn(sr, __dmul_rn(pi, a.sin_t));
-                si = __dadd_rn(si, -__dmul_rn(pr, a.sin_t));
+                sr = __dadd_rn(__dadd_rn(0.0, sr), __dmul_rn(pi, a.sin_t));
+                si = __dadd_rn(__dadd_rn(0.0, si), -__dmul_rn(pr, a.sin_t));
                 s_coef[r] = f64x2{sr, si};                                     // final; an unmatched row keeps c: cos c and the new row's
                 cls |= CL_MATCHED;                                             // coefficient are formed from it when they are written
             } else {                                                           // its product row is new
                 phase_mul(c.x, c.y, (info >> 1) & 3, pr, pi);
-                if (res_keep(__dmul_rn(pi, a.sin_t), -__dmul_rn(pr, a.sin_t), a.thr)) cls |= CL_N;
+                if (above_thr(__dmul_rn(pi, a.sin_t), -__dmul_rn(pr, a.sin_t), a.thr)) cls |= CL_N;
             }
-            if (res_keep(sr, si, a.thr)) cls |= CL_A;
+            if (above_thr(sr, si, a.thr)) cls |= CL_A;
             s_cls[r] = cls;
         }
     } else {
@@ -463,7 +460,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
             } else {
                 const f64x2 c = s_coef[r];
                 if (k & 1) {
-                    if (res_keep(c.x, c.y, a.thr)) {
+                    if (above_thr(c.x, c.y, a.thr)) {
                         double x, y;
                         phase_mul(c.x, c.y, (info >> 1) & 3, x, y);
                         double pr = y, pi = -x;                                // c * i^e * (-i)
@@ -549,7 +546,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
         for (int r2 = tid; r2 < Rw; r2 += RES_THREADS)
             if (s_cls[r2] & CL_C) {
                 const i64 d = (i64)prefC + s_pos[r2];
-                out_coeff2[d] = s_coef[r2];
+                out_coeff2[d] = plus_zero(s_coef[r2]);                         // 0 + c: the reference's cleanup sums into zeros (-0 -> +0)
                 if (a.out_hash) a.out_hash[d] = a.hin[row0 + r2];
             }
     }
@@ -612,7 +609,8 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
             }
             if (cl & CL_A) {
                 const i64 d = baseA + s_pos[r2];
-                out_coeff2[d] = (cl & CL_MATCHED) ? c : f64x2{__dmul_rn(c.x, a.cos_t), __dmul_rn(c.y, a.cos_t)};
+                const f64x2 ca = (cl & CL_MATCHED) ? c : f64x2{__dmul_rn(c.x, a.cos_t), __dmul_rn(c.y, a.cos_t)};
+                out_coeff2[d] = MODE == 0 ? plus_zero(ca) : ca;
                 if (a.out_hash) a.out_hash[d] = h;
             }
             if (cl & CL_N) {
@@ -621,7 +619,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
                 if (MODE == 0) {                                               // (-i sin) i^e c, from the row's own coefficient
                     double pr, pi;
                     phase_mul(c.x, c.y, (s_info[r2] >> 1) & 3, pr, pi);
-                    cn = f64x2{__dmul_rn(pi, a.sin_t), -__dmul_rn(pr, a.sin_t)};
+                    cn = plus_zero(f64x2{__dmul_rn(pi, a.sin_t), -__dmul_rn(pr, a.sin_t)});
                 }
                 out_coeff2[d] = cn;
                 if (a.out_hash) a.out_hash[d] = h ^ a.hq;

@@ -633,7 +633,7 @@ class PauliwordOp:
             angle = np.pi / 2
         if angle.imag != 0:
             warnings.warn('Complex component in angle: this will be ignored.')
-        angle = angle.real
+        angle = float(np.real(angle))                           # a 0-d ndarray is not hashable: kernels.rotation_args is cached per angle
         assert Pword.n_terms == 1, 'Only rotation by single Pauliword allowed here'
         assert Pword.n_qubits == self.n_qubits, 'Pauliwords defined for different number of qubits'
         if Pword._c()[0] != 1:

@@ -1,0 +1,218 @@
+"""GPU: the keep rule np.abs(c) > thr (utils.py:275-278) where it is fragile, on every cleanup and rotation path the library's switches
+force.  Edge coefficients — |c| at thr and a few ulp around it, signed zeros, subnormals, NaN and inf, merges that cancel or overflow —
+are planted among ordinary ones, as single terms and as the first or last member of a merged segment.  Expected results come from the
+fixture the reference produced (tests/golden/coeff_edges.npz, which both oracles match on the CPU) or from the oracles.
+
+Coefficients are compared as bits: signed zeros included, NaN positions equal (a NaN's sign and payload are not compared: a NaN that an
+operation creates is negative on x86-64 and positive on the GPU).  Where the device's product rule (the plain, unfused
+product, the phase applied exactly) does not give NumPy's FMA product bit for bit — non-finite factors, general inexact coefficients; the
+fixture's ``exact`` flag — products are compared with the C oracle, which states that rule, and rotations path against path."""
+import numpy as np
+import pytest
+from symmer_amd import PauliwordOp, kernels
+from oracle import oracle_np as onp
+from oracle import oracle_c as oc
+from _golden import family, as_bool
+
+pytestmark = pytest.mark.gpu
+
+CLEANUP_PATHS = {'default': {}, 'lazy off': {'SYMGPU_CLEANUP_LAZY': '0'}, 'lazy on': {'SYMGPU_CLEANUP_LAZY': '1'},
+                 'no floor': {'SYMGPU_CLEANUP_NOFLOOR': '1'}, 'emit fused': {'SYMGPU_EMIT_FUSED': '1'},
+                 'emit unfused': {'SYMGPU_EMIT_FUSED': '0'}}
+MUL_PATHS = {'default': {}, 'full sort': {'SYMGPU_CLEANUP_SUSPECTS': '0'}, 'give up': {'SYMGPU_CLEANUP_SUSPECTS': '2'},
+             'sorted flag pass': {'SYMGPU_CLEANUP_DIRECT': '0'}, 'key words': {'SYMGPU_CLEANUP_KEYBYTES': '0'},
+             'unpacked': {'SYMGPU_CLEANUP_UNPACKED': '1'}, 'no floor': {'SYMGPU_CLEANUP_NOFLOOR': '1'},
+             'lazy off': {'SYMGPU_CLEANUP_LAZY': '0'}, 'no square': {'SYMGPU_CLEANUP_NOSQUARE': '1'}}
+ROT_PATHS = {'resident': {}, 'general': {'SYMGPU_ROTATE_GENERAL': '1'}, 'rows in memory': {'SYMGPU_ROT_HBM': '2'}}
+CASES = family('coeff_edges')
+KIND = ('cleanup', 'mul', 'rotate')
+
+
+def _of(kind):
+    return [pytest.param(c, id=f"{i}-{c['family']}") for i, c in enumerate(CASES) if KIND[int(c['kind'])] == kind]
+
+
+def _set(monkeypatch, env):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def assert_bits(rows, coeff, exp_rows, exp_coeff, what='', zero_sign=True):
+    """rows and order equal; coefficient components equal as uint64, NaN where NaN is expected.  zero_sign=False: a zero component
+    compares by value (the Clifford branch)."""
+    rows, exp_rows = np.asarray(rows), np.asarray(exp_rows)
+    assert rows.shape == exp_rows.shape, (what, rows.shape, exp_rows.shape)
+    assert np.array_equal(rows, exp_rows), what
+    got = np.ascontiguousarray(coeff, dtype=np.complex128).view(np.float64)
+    exp = np.ascontiguousarray(exp_coeff, dtype=np.complex128).view(np.float64)
+    if not zero_sign:
+        got, exp = np.where(got == 0, 0.0, got), np.where(exp == 0, 0.0, exp)
+    assert np.array_equal(np.isnan(got), np.isnan(exp)), what
+    m = ~np.isnan(exp)
+    bad = np.flatnonzero(got[m].view(np.uint64) != exp[m].view(np.uint64))
+    assert bad.size == 0, (what, bad.size, [(float(got[m][i]), float(exp[m][i])) for i in bad[:4]])
+
+
+def _clifford(angle):
+    m = float(angle) * 2 / np.pi
+    return abs(round(m) - m) <= 1e-18
+
+
+@pytest.mark.parametrize('path', list(CLEANUP_PATHS))
+@pytest.mark.parametrize('case', _of('cleanup'))
+def test_cleanup_edges(case, path, monkeypatch):
+    _set(monkeypatch, CLEANUP_PATHS[path])
+    symp = as_bool(case['in_symp']); n = symp.shape[1] // 2
+    thr = float(case['thr']) if case['has_thr'] else None
+    rows, c = kernels.cleanup(onp.pack_rows(symp), case['in_coeff'], thr)
+    assert_bits(onp.unpack_rows(rows, n), c, case['out_symp'], case['out_coeff'], what=path)
+
+
+@pytest.mark.parametrize('path', list(MUL_PATHS))
+@pytest.mark.parametrize('case', _of('mul'))
+def test_product_edges(case, path, monkeypatch):
+    """P * Q and P * P (squared: the twins summed first, dyadic values so that the sums are exact) with a threshold; the indexed product
+    on the default path.  Products NumPy's FMA forms differently (``exact`` False): the C oracle's plain product (the device rule)."""
+    _set(monkeypatch, MUL_PATHS[path])
+    a = as_bool(case['in_symp']); b = as_bool(case['b_symp']); n = a.shape[1] // 2
+    thr = float(case['thr'])
+    A, ca = onp.pack_rows(a), np.asarray(case['in_coeff'], dtype=complex)
+    if case['family'] == 'squared':
+        rows, c = kernels.mul_cleanup(A, ca, A, ca, True, thr)
+    else:
+        rows, c = kernels.mul_cleanup(A, ca, onp.pack_rows(b), case['b_coeff'], True, thr)
+    if case['exact']:
+        exp = case['out_symp'], case['out_coeff']
+    else:
+        er, ec = oc.mul(A, ca, onp.pack_rows(b), case['b_coeff'], thr)
+        exp = onp.unpack_rows(er, n), ec
+    assert_bits(onp.unpack_rows(rows, n), c, *exp, what=path)
+    if path == 'default' and case['family'] != 'squared':
+        rows, c, _, _ = kernels.mul_cleanup_indexed(A, ca, onp.pack_rows(b), case['b_coeff'], True, thr)
+        assert_bits(onp.unpack_rows(rows, n), c, *exp, what='indexed')
+
+
+def _first_rows(symp, coeff):
+    """the operator without repeated rows (the first copy of each kept): what the resident kernel takes"""
+    _, first = np.unique(symp, axis=0, return_index=True)
+    first = np.sort(first)
+    return symp[first], coeff[first]
+
+
+@pytest.mark.parametrize('path', list(ROT_PATHS))
+@pytest.mark.parametrize('case', _of('rotate'))
+def test_rotation_edges(case, path, monkeypatch):
+    """_rotate_by_single_Pword with a 0-d ndarray angle (exact multiples of pi/2, multiples 1e-18 off — the Clifford-detection threshold —,
+    negative angles, non-Clifford ones): the operator as planted (repeated rows: the merging path) and without its repeated rows."""
+    _set(monkeypatch, ROT_PATHS[path])
+    symp, coeff, q = as_bool(case['in_symp']), np.asarray(case['in_coeff'], dtype=complex), as_bool(case['q'])
+    ang = np.array(float(case['angle']))
+    Q = PauliwordOp(q.reshape(1, -1), [1])
+    zs = not _clifford(ang)
+    us, uc = _first_rows(symp, coeff)
+    P = PauliwordOp(symp, coeff)
+    R = P._rotate_by_single_Pword(Q, ang)
+    assert (R is P) == bool(case['same_object'])
+    if not case['exact']:
+        # non-finite coefficients through cos / sin and the phase follow the device rule, which no oracle states: this path
+        # gives the bits of another one (the general multi-launch path; for that one, the default)
+        other = {} if path == 'general' else ROT_PATHS['general']
+        for ops in ((symp, coeff), (us, uc)):
+            R = PauliwordOp(*ops)._rotate_by_single_Pword(Q, ang)
+            for k in ('SYMGPU_ROTATE_GENERAL', 'SYMGPU_ROT_HBM'):
+                monkeypatch.delenv(k, raising=False)
+            _set(monkeypatch, other)
+            D = PauliwordOp(*ops)._rotate_by_single_Pword(Q, ang)
+            for k in ('SYMGPU_ROTATE_GENERAL', 'SYMGPU_ROT_HBM'):
+                monkeypatch.delenv(k, raising=False)
+            _set(monkeypatch, ROT_PATHS[path])
+            assert_bits(R.symp_matrix, R.coeff_vec, D.symp_matrix, D.coeff_vec, what=path, zero_sign=zs)
+        return
+    if zs and us.shape[0] < symp.shape[0]:
+        # repeated rows, not Clifford: one fused cleanup instead of the reference's three (<= 1e-16 relative)
+        assert np.array_equal(R.symp_matrix, as_bool(case['out_symp'])), path
+        assert np.allclose(R.coeff_vec, case['out_coeff'], rtol=1e-15, atol=0), path
+    else:
+        assert_bits(R.symp_matrix, R.coeff_vec, case['out_symp'], case['out_coeff'], what=path, zero_sign=zs)
+    R = PauliwordOp(us, uc)._rotate_by_single_Pword(Q, ang)
+    assert_bits(R.symp_matrix, R.coeff_vec, *onp.rotate_by_single_pword(us, uc, q, ang), what=path + ', no repeated rows', zero_sign=zs)
+    # after a cleanup the library knows the operator has no repeated rows: the one-launch resident kernel takes it
+    cs, cc = onp.cleanup_op(us, uc)
+    R = PauliwordOp(us, uc).cleanup()._rotate_by_single_Pword(Q, ang)
+    assert_bits(R.symp_matrix, R.coeff_vec, *onp.rotate_by_single_pword(cs, cc, q, ang), what=path + ', after cleanup', zero_sign=zs)
+
+
+def test_rotation_chain_edges():
+    """a short chain (perform_rotations: Clifford and not, a negative angle) of an operator with coefficients at the threshold"""
+    case = next(c for c in CASES if KIND[int(c['kind'])] == 'rotate' and c['family'] == 'boundary')
+    symp, coeff = _first_rows(as_bool(case['in_symp']), np.asarray(case['in_coeff'], dtype=complex))
+    rng = np.random.default_rng(77)
+    n = symp.shape[1] // 2
+    rots = []
+    for ang in (np.pi / 2, 0.3, -np.pi / 2, np.pi, -1.1):
+        q = rng.random(2 * n) < 0.4
+        q[0] = True
+        rots.append((q, ang))
+    R = PauliwordOp(symp, coeff).perform_rotations([(PauliwordOp(q.reshape(1, -1), [1]), a) for q, a in rots])
+    assert_bits(R.symp_matrix, R.coeff_vec, *onp.perform_rotations(symp, coeff, [(q, a) for q, a in rots]), zero_sign=False)
+
+
+def _edges(thr):
+    up, dn = np.nextafter(thr, 1.0), np.nextafter(thr, 0.0)
+    x = thr / np.sqrt(2.0)
+    return np.array([thr, dn, up, np.nextafter(up, 1.0), -thr, 1j * thr, 1j * dn, -1j * up, complex(thr, 5e-324), complex(x, x),
+                     complex(np.nextafter(x, 1.0), x), complex(-x, np.nextafter(x, 0.0)), 0.0, complex(-0.0, -0.0), 5e-324,
+                     complex(2.2e-308, -1e-310)])
+
+
+@pytest.mark.parametrize('path', [p for p in MUL_PATHS if p != 'no square'])
+def test_gated_product_edges(path, monkeypatch):
+    """Above the 2^22-key gate (the shapes of test_gpu_fullsize: 100 qubits, 2600 x 2100 terms — the flag pass, the lazy flow): edge
+    coefficients in the inner operand against outer coefficients 1, -1, i and 0.5 (exact products at the threshold), and the coefficient
+    floor shortcut (all operand components non-zero: every pair kept unseen) switched off by one term (inf, inf) against a term (1, 0),
+    whose plain product is (NaN, NaN)."""
+    _set(monkeypatch, MUL_PATHS[path])
+    rng = np.random.default_rng(9090)
+    n, na, nb, thr = 100, 2600, 2100, 1e-15
+    nz = lambda t: (rng.integers(1, 9, t) * rng.choice([-1, 1], t) + 1j * rng.integers(1, 9, t) * rng.choice([-1, 1], t)) / 16.0
+    sa = rng.random((na, 2 * n)) < 0.3; sb = rng.random((nb, 2 * n)) < 0.3
+    ca, cb = nz(na), nz(nb)
+    e = _edges(thr)
+    ca[rng.choice(na, e.size, replace=False)] = e
+    cb[:4] = [1.0, -1.0, 1j, 0.5]
+    for plant in ('edges', 'floor'):
+        if plant == 'floor':
+            ca, cb = nz(na), nz(nb)
+            ca[1234] = complex(np.inf, np.inf); cb[7] = 1.0
+        A, B = onp.pack_rows(sa), onp.pack_rows(sb)
+        rows, c = kernels.mul_cleanup(A, ca, B, cb, True, thr)
+        er, ec = oc.mul(A, ca, B, cb, thr)
+        assert rows.shape[0] > (1 << 21)
+        assert_bits(rows, c, er, ec, what=f'{path}, {plant}')
+
+
+@pytest.mark.parametrize('path', ['default', 'no square'])
+def test_gated_squared_edges(path, monkeypatch):
+    """P * P of 3000 terms (4.5e6 keys: the lazy flow) with dyadic coefficients and thr = 1/256: products of two 1/16 components and the
+    twin sums 2 * 1/512 land exactly on the threshold (strict: dropped)."""
+    _set(monkeypatch, MUL_PATHS[path])
+    rng = np.random.default_rng(2207)
+    n, t, thr = 100, 3000, 1.0 / 256
+    s = rng.random((t, 2 * n)) < 0.3
+    c = (rng.integers(-4, 5, t) + 1j * rng.integers(-4, 5, t)) / 16.0
+    c[rng.choice(t, 200, replace=False)] = rng.choice([1 / 16, -1j / 16, 1 / 32 + 1j / 32, 1 / 64], 200)
+    A = onp.pack_rows(s)
+    rows, got = kernels.mul_cleanup(A, c, A, c, True, thr)
+    assert_bits(rows, got, *oc.mul(A, c, A, c, thr), what=path)
+
+
+def test_nan_beside_a_large_component_is_dropped(monkeypatch):
+    """(NaN, 5) with thr = 1: np.abs gives NaN, so the reference drops it — on the marking of single terms (lazy flow) as on the sums"""
+    rng = np.random.default_rng(5)
+    symp = rng.random((40, 20)) < 0.4
+    coeff = np.ones(40, dtype=complex); coeff[3] = complex(np.nan, 5.0); coeff[11] = complex(5.0, np.nan); coeff[17] = complex(np.inf, np.nan)
+    er, ec = onp.symplectic_cleanup(symp, coeff, 1.0)
+    for lazy in ('0', '1'):
+        monkeypatch.setenv('SYMGPU_CLEANUP_LAZY', lazy)
+        rows, c = kernels.cleanup(onp.pack_rows(symp), coeff, 1.0)
+        assert_bits(onp.unpack_rows(rows, 10), c, er, ec, what=f'lazy={lazy}')

@@ -306,3 +306,23 @@ def test_lexicographic_order_from_packed_rows_equals_numpy_lexsort_of_the_column
         Q = P.sort('lex')
         assert np.array_equal(Q.symp_matrix, m[np.lexsort(m.T)]) and np.array_equal(Q.coeff_vec, np.lexsort(m.T).astype(complex))
     assert PauliwordOp(np.zeros((0, 6), dtype=bool), [])._lex_order().size == 0
+
+
+@pytest.mark.parametrize('angle', [np.pi / 2, -np.pi / 2, np.pi, -np.pi, 3 * np.pi / 2, -3 * np.pi / 2, 2 * np.pi, 0.0, -0.0, 0.3, -1.1,
+                                   np.pi / 2 * 1e-18, np.pi / 2 * 0.9e-18, np.pi / 2 * 2e-18, -np.pi / 2 * 1e-18, -np.pi / 2 * 2e-18])
+def test_rotation_args_clifford_detection(angle):
+    """The reference's Clifford branch (base.py:1146-1154): multiple = 2 angle / pi, int_part = round(multiple); Clifford iff
+    |int_part - multiple| <= 1e-18; odd int_part multiplies by Q; int_part in [2, 3] negates.  rotation_args must decide the same for the
+    float _rotate_by_single_Pword hands it, whether the caller's angle was a float, a 0-d ndarray or a complex 0-d ndarray."""
+    from symmer_amd import kernels
+    for given in (angle, np.array(angle), np.array(complex(angle, 0.0)), np.float64(angle)):
+        assert kernels.rotation_args(float(np.real(given))) == kernels.rotation_args(angle)
+    cos_t, sin_t, k = kernels.rotation_args(angle)
+    multiple = angle * 2 / np.pi
+    int_part = round(multiple)
+    if abs(int_part - multiple) <= 1e-18:
+        assert k >= 0
+        assert (k & 1) == (int_part % 2)                    # multiplies by Q
+        assert (k in (2, 3)) == (int_part in (2, 3))        # negates
+    else:
+        assert k == -1 and cos_t == np.cos(angle) and sin_t == np.sin(angle)

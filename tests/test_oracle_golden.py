@@ -187,3 +187,37 @@ def test_sort_orders_golden(case):
         for key in ('decreasing', 'increasing'):
             order = onp.sort_order(symp, coeff, by, key)
             assert np.array_equal(symp[order], as_bool(case[f'sort_{by}_{key}_symp'])) and np.array_equal(coeff[order], case[f'sort_{by}_{key}_coeff']), (by, key)
+
+
+def _bits(c):
+    """complex128 -> uint64 pairs: NaN positions, signed zeros and every other bit compared as they are"""
+    return np.ascontiguousarray(np.asarray(c, dtype=np.complex128)).view(np.uint64)
+
+
+def _assert_same_bits(rows, coeff, exp_rows, exp_coeff):
+    assert as_bool(rows).shape == as_bool(exp_rows).shape and np.array_equal(as_bool(rows), as_bool(exp_rows))
+    assert np.array_equal(_bits(coeff), _bits(exp_coeff))
+
+
+@pytest.mark.parametrize('case', family('coeff_edges'), ids=lambda c: f"{['cleanup', 'mul', 'rotate'][int(c['kind'])]}-{c['family']}")
+def test_coeff_edges(case):
+    """The keep rule np.abs(c) > thr where it is fragile — |c| at thr and a few ulp around it, signed zeros, subnormals, NaN and inf,
+    merges that cancel or overflow — in cleanups, products and rotations (oracle/tools/gen_golden_coeff_edges.py): the NumPy oracle bit
+    for bit everywhere, the C oracle bit for bit wherever its plain complex product is NumPy's FMA product (``exact``)."""
+    kind, thr = int(case['kind']), float(case['thr'])
+    a = as_bool(case['in_symp']); n = _n(a)
+    exp = case['out_symp'], case['out_coeff']
+    if kind == 0:
+        got = onp.symplectic_cleanup(a, case['in_coeff'], thr if case['has_thr'] else None)
+        _assert_same_bits(*got, *exp)
+        rows, c = oc.cleanup(onp.pack_rows(a), case['in_coeff'], thr if case['has_thr'] else None)
+        _assert_same_bits(onp.unpack_rows(rows, n), c, *exp)
+    elif kind == 1:
+        b = as_bool(case['b_symp'])
+        _assert_same_bits(*onp.multiply_by_operator(a, case['in_coeff'], b, case['b_coeff'], thr), *exp)
+        if case['exact']:
+            rows, c = oc.mul(onp.pack_rows(a), case['in_coeff'], onp.pack_rows(b), case['b_coeff'], thr)
+            _assert_same_bits(onp.unpack_rows(rows, n), c, *exp)
+    else:
+        ang = float(case['angle'])
+        _assert_same_bits(*onp.rotate_by_single_pword(a, case['in_coeff'], as_bool(case['q']), np.array(ang)), *exp)
