@@ -253,6 +253,22 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
 int symgpu_noncontextual_dev(symgpu_op_t op, int *is_noncontextual);
 int symgpu_state_inner_dev(symgpu_op_t a, symgpu_op_t b, double *out);
 
+/* ---- f5: PauliwordOp.to_sparse_matrix (base.py:1458-1507) of a resident operator, n_qubits 1 .. 31, as CSR (csrc/sparse_matrix.hip) -------
+ * Entry (b, b ^ x_k) = sum over terms k, in operator order, of c_k (-i)^{Y_k} (-1)^{|b & z_k|}; qubit 0 is the MOST significant bit of
+ * b and of x_k, z_k.  Duplicate terms are summed, the operator is not cleaned first; entries whose two components are both +-0 are not
+ * stored, NaN / inf ones are.  Columns ascend within a row.
+ * symgpu_to_csr_count   groups the terms by X-part, counts the kept entries of every row and scans them into a 64-bit indptr, all on the
+ *   operator's device; *nnz = the exact entry count, *fill_scratch_bytes = the device scratch the fill will allocate besides its output
+ *   (data, indices, and an int32 indptr when index_bytes = 4).  The grouped terms and indptr stay on the device in *plan (the operator is
+ *   not referenced again).
+ * symgpu_to_csr_fill    consumes the plan: data (complex128 [nnz]), indices ([nnz]) and indptr ([2^n + 1]), both of index_bytes = 4
+ *   (int32) or 8 (int64), written into host buffers; every device buffer of the plan is freed before it returns, also on failure.
+ *   All three buffers NULL: the plan is only freed (a caller that cannot hold the output).  SYMGPU_CSR_SCRATCH=1 forces the fill's
+ *   global-scratch form (taken by itself when a row's groups do not fit the LDS). */
+typedef struct symgpu_csr_s *symgpu_csr_t;
+int symgpu_to_csr_count(symgpu_op_t op, int n_qubits, int64_t *nnz, int64_t *fill_scratch_bytes, symgpu_csr_t *plan);
+int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *indptr, int index_bytes);
+
 /* ---- e: multi-GPU (one process per GPU; RCCL over xGMI) ------------------------------------------- */
 #define SYMGPU_UNIQUE_ID_BYTES 128
 int symgpu_comm_available(void);                                                /* librccl loadable? (no device, no collective) */

@@ -102,6 +102,8 @@ SIGNATURES = {
     'symgpu_project_dev': [P, P, c_int, P, P, c_int, c_int, c_dbl, c_int, PP, P],
     'symgpu_noncontextual_dev': [P, P],
     'symgpu_state_inner_dev': [P, P, P],
+    'symgpu_to_csr_count': [P, c_int, P, P, PP],
+    'symgpu_to_csr_fill': [P, P, P, P, c_int],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

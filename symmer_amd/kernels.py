@@ -514,6 +514,62 @@ def state_inner_dev(a, b):
     return complex(out[0], out[1])
 
 
+def _host_available_bytes():
+    """MemAvailable of /proc/meminfo (None where there is no such file)."""
+    try:
+        with open('/proc/meminfo') as f:
+            for line in f:
+                if line.startswith('MemAvailable:'):
+                    return int(line.split()[1]) * 1024
+    except OSError:
+        pass
+    return None
+
+
+def csr_index_dtype(nnz, n_qubits):
+    """The index dtype scipy gives a ``2^n x 2^n`` CSR matrix of ``nnz`` entries: int32 while both fit, else int64."""
+    return np.int32 if max(int(nnz), 1 << int(n_qubits)) <= np.iinfo(np.int32).max else np.int64
+
+
+def to_csr(devop, n_qubits):
+    """``PauliwordOp.to_sparse_matrix`` (base.py:1458-1507) of a device operator of 1 <= n_qubits <= 31 as ``(data, indices, indptr)``
+    NumPy arrays of a canonical ``2^n x 2^n`` CSR matrix: entry (b, b ^ x_k) sums ``c_k (-i)^{Y_k} (-1)^{|b & z_k|}`` over the terms in
+    operator order, qubit 0 the most significant bit of b; entries whose two components are both +-0 are not stored.  The exact entry
+    count is known before the output is allocated: MemoryError if it does not fit the device or the host."""
+    n_qubits = int(n_qubits)
+    if not 1 <= n_qubits <= 31:
+        raise ValueError(f'to_csr: n_qubits = {n_qubits} outside 1 .. 31 (column indices must fit an int32 index space)')
+    nnz_c, scratch_c, plan = c_i64(0), c_i64(0), ctypes.c_void_p()
+    check(_lib.lib().symgpu_to_csr_count(devop.handle, n_qubits, ctypes.addressof(nnz_c), ctypes.addressof(scratch_c), ctypes.byref(plan)))
+    nnz, side = int(nnz_c.value), 1 << n_qubits
+    idx_dtype = csr_index_dtype(nnz, n_qubits)
+    ib = np.dtype(idx_dtype).itemsize
+    host_need = nnz * (16 + ib) + (side + 1) * ib
+    # what the fill allocates on the device: data + indices, the int32 copy of indptr (the int64 one is already held by the plan, so the
+    # free memory read below has paid for it) and its slot scratch, as the count call reports it
+    dev_need = nnz * (16 + ib) + ((side + 1) * 4 if ib == 4 else 0) + int(scratch_c.value)
+    free_b, total_b = c_i64(0), c_i64(0)
+    rc = _lib.lib().symgpu_mem_info(ctypes.addressof(free_b), ctypes.addressof(total_b))
+    host_avail = _host_available_bytes()
+    short = None
+    if rc == 0 and dev_need > free_b.value:
+        short = f'{dev_need / 2**30:.2f} GiB on the device, {free_b.value / 2**30:.2f} GiB free'
+    elif host_avail is not None and host_need > host_avail:
+        short = f'{host_need / 2**30:.2f} GiB on the host, {host_avail / 2**30:.2f} GiB available'
+    if short is not None:
+        check(_lib.lib().symgpu_to_csr_fill(plan, None, None, None, ib))          # frees the plan
+        raise MemoryError(f'to_sparse_matrix: {nnz} entries of a {side} x {side} matrix need {short}')
+    try:
+        data = np.empty(nnz, dtype=np.complex128)
+        indices = np.empty(nnz, dtype=idx_dtype)
+        indptr = np.empty(side + 1, dtype=idx_dtype)
+    except MemoryError:
+        check(_lib.lib().symgpu_to_csr_fill(plan, None, None, None, ib))
+        raise
+    check(_lib.lib().symgpu_to_csr_fill(plan, addr(data), addr(indices), addr(indptr), ib))
+    return data, indices, indptr
+
+
 # ---- cleanups that also return the first-occurrence index of every output term (hash-partitioned multi-GPU cleanup, parallel.py) ----
 def _first_index(op):
     t = op.n_terms

@@ -1,9 +1,10 @@
 """``PauliwordOp`` — drop-in for the reference class on the symplectic hot path
 (``symmer/operators/base.py:33-1561``): same constructor, attributes, methods, exceptions and results for
 construction, ``+ - *``, ``cleanup``, commutation/adjacency, single-Pauli rotations and GF(2) generator
-routines.  The data-parallel work runs in hand-written HIP kernels (``libsymgpu.so``); host code is NumPy
-glue only.  Out of scope (not on the path): ``from_matrix``, ``to_sparse_matrix``, graph colouring,
-openfermion/qiskit converters, ``QuantumState``.
+routines, and ``to_sparse_matrix`` (a scipy CSR matrix built on the device, csrc/sparse_matrix.hip).  The
+data-parallel work runs in hand-written HIP kernels (``libsymgpu.so``); host code is NumPy glue only.  Out of
+scope (not on the path): ``from_matrix``, graph colouring, openfermion/qiskit converters;
+``QuantumState`` lives in quantum_state.py.
 """
 import warnings
 from copy import deepcopy
@@ -731,6 +732,24 @@ class PauliwordOp:
     def to_dictionary(self) -> Dict[str, complex]:
         op = self.cleanup()
         return {symplectic_to_string(v): c for v, c in zip(op.symp_matrix, op._c())}
+
+    @cached_property
+    def to_sparse_matrix(self):
+        """base.py:1458-1507: the ``2^n x 2^n`` matrix of the operator as a canonical ``scipy.sparse.csr_matrix`` (complex128), the
+        Kronecker product ``P_0 x P_1 x ... x P_{n-1}`` of every term summed over the terms: qubit 0 is the most significant bit of the
+        row and column index, duplicate terms are summed in operator order (the operator is not cleaned first), and entries that cancel
+        to an exact zero are not stored.  Built on the device (``kernels.to_csr``) for n <= 31 qubits; ValueError beyond, MemoryError
+        when the output does not fit.  A cached property, as in the reference: the matrix does NOT follow later changes of ``coeff_vec``."""
+        from scipy.sparse import csr_matrix
+        if self.n_qubits == 0:
+            return csr_matrix(self.coeff_vec)
+        if self.n_qubits > 31:
+            raise ValueError(f'to_sparse_matrix: {self.n_qubits} qubits; at most 31 (column indices must fit an int32 index space)')
+        side = 1 << self.n_qubits
+        if self.n_terms == 0:
+            return csr_matrix((side, side), dtype=np.complex128)
+        data, indices, indptr = kernels.to_csr(self._device(), self.n_qubits)
+        return csr_matrix((data, indices, indptr), shape=(side, side))
 
     # ---- a10 / f2: GF(2) generator routines (same device kernel as a8) ----------------------------------------
     @cached_property

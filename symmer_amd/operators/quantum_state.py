@@ -3,7 +3,8 @@
 A sparse statevector is carried as a ``PauliwordOp`` (``|0> -> Z``, ``|1> -> X``, base.py:1564-1580), so applying an operator
 to a state is the SAME device path as operator x operator: the fused all-pairs product + cleanup kernel, followed by the
 ``i^{Y}`` post-factor (base.py:854-857).  Expectation values reuse it (base.py:796-819, 2438-2471).
-Not provided (dense/sparse matrices, sampling, partial traces, plotting): outside the accelerated path.
+Sparse and dense vectors (``to_sparse_matrix``, ``to_dense_matrix``, base.py:1994-2023) are host code.  Not provided (sampling,
+partial traces, plotting): outside the accelerated path.
 """
 from copy import deepcopy
 from functools import cached_property
@@ -151,6 +152,26 @@ class QuantumState:
     @cached_property
     def dagger(self) -> "QuantumState":
         return QuantumState(self.state_matrix, self.state_op.coeff_vec.conjugate(), vec_type='bra' if self.vec_type == 'ket' else 'ket')
+
+    @cached_property
+    def to_sparse_matrix(self):
+        """base.py:1994-2014: the state as a ``scipy.sparse.csr_matrix`` (complex128) — a ket is a ``(2^n, 1)`` column, a bra a
+        ``(1, 2^n)`` row (its coefficients are already conjugated).  Basis string ``s`` sits at index ``int(s, 2)`` (qubit 0 the most
+        significant bit, as in ``PauliwordOp.to_sparse_matrix``); repeated basis strings are summed.  Cached, like the reference's."""
+        from scipy.sparse import csr_matrix
+        n = self.n_qubits
+        weights = np.array([1 << (n - 1 - q) for q in range(n)], dtype=object if n >= 63 else np.int64)
+        index = self.state_matrix @ weights if n else np.zeros(self.n_terms, dtype=np.int64)
+        zeros = np.zeros_like(index)
+        coeff = np.asarray(self.state_op.coeff_vec, dtype=np.complex128)
+        shape = (1 << n, 1) if self.vec_type != 'bra' else (1, 1 << n)
+        rc = (index, zeros) if self.vec_type != 'bra' else (zeros, index)
+        return csr_matrix((coeff, rc), shape=shape, dtype=np.complex128)
+
+    @cached_property
+    def to_dense_matrix(self) -> np.ndarray:
+        """base.py:2016-2023: ``to_sparse_matrix`` as a dense ndarray of the same shape."""
+        return self.to_sparse_matrix.toarray()
 
     def _is_normalized(self) -> bool:
         return bool(np.isclose(np.linalg.norm(self.state_op.cleanup().coeff_vec), 1))
