@@ -67,13 +67,13 @@ struct Context {
     u64 hash_seed = 0;
     std::vector<u64> host_hash_tab;  // host copy of hash_tab (to hash single rows, e.g. a rotation's Q, with the SAME device's tables)
     u64 *xs_pow = nullptr;         // device, [32][64]: columns of M^(2^j), M = the hash's xorshift step (k_hash_rows_long, cleanup_hash.hip)
-    // rotation hash join (rotate.hip): persistent open-addressing table of [tag 32 | generation 10 | row index + 1 : 22] entries.
+    // rotation hash join (rotate_analyze.hip, rotate_fast.hip): persistent open-addressing table of [tag 32 | generation 10 | row index + 1 : 22] entries.
     // An entry of another generation is empty, so the table is cleared once per 1023 rotations instead of once per rotation.
     u64 *rot_table = nullptr;
     size_t rot_table_cap = 0;      // entries (power of two)
     u32 rot_gen = 0;
     u32 *rot_flags = nullptr;      // device u32[4]: [0] = generation in which a duplicate input row was seen
-    void *rot_host_cnt = nullptr, *rot_host_cnt_dev = nullptr;   // pinned host copy of a rotation's counts and its device address (rotate.hip)
+    void *rot_host_cnt = nullptr, *rot_host_cnt_dev = nullptr;   // pinned host copy of a rotation's counts and its device address (rotate_analyze.hip)
     // one-launch rotation (rotate_resident.hip): partner notes [generation 10 | row + 1 : 22] of the join (same generation as
     // rot_table), the granules of the in-launch all-gathers + failure words, and the epoch that tags them (1 .. 16382)
     u32 *rot_partner = nullptr;
@@ -166,7 +166,7 @@ struct symgpu_op_s {
     u64 *wm = nullptr;
     i64 wm_pad = 0, wm_T = -1;
     // 1 = known to hold no two equal rows (result of a cleanup, or of a rotation of such an operator); 0 = unknown.
-    // Reset by op_invalidate, i.e. whenever rows change.  The odd-k Clifford rotation needs to know (rotate.hip).
+    // Reset by op_invalidate, i.e. whenever rows change.  The odd-k Clifford rotation needs to know (rotate_driver.hip).
     int dup_free = 0;
     // cached linear row hashes h1 of rows[0..T) under hash seed `hash_seed` (0 = none): a rotation hands them on to its result
     // for free (h(P ^ Q) = h(P) ^ h(Q)), so a chain of rotations hashes the operator once.  Dropped by op_invalidate.

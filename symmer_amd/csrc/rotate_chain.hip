@@ -5,7 +5,7 @@
 // For a clean operator (no duplicate rows, every |c| above the threshold — what cleanup() leaves and what a Clifford rotation
 // preserves) one rotation by angle k pi/2 is:  rows that anticommute with Q get  row ^= Q, c *= i^e (-i)  (odd k) and  c = -c
 // (k in {2, 3});  then the operator is re-ordered  [anticommuting rows | commuting rows], both parts in their previous order — a
-// STABLE PARTITION.  The multi-launch forms of rotate.hip materialise that partition after every rotation (two launches and 54 MB of
+// STABLE PARTITION.  The multi-launch forms (rotate_chain_forms.hip) materialise that partition after every rotation (two launches and 54 MB of
 // traffic per rotation at 10^5 terms of 1,000 qubits: 20 us).  But nothing in the next rotation depends on the ORDER of the rows —
 // flags, phases and coefficients are functions of the row alone.  K stable partitions by the bits b_1 .. b_K (b = 0: anticommuting)
 // are one stable LSD radix sort by the K-bit number b_K ... b_1.  So:
@@ -18,7 +18,7 @@
 //   radix sort     of the keys [partition bits : <= 40 | original index : 22] (sort.hip, stable, 8 bits per pass)
 //   k_cchain_permute  rows and coefficients to their final places (one gather of whole rows).
 //
-// Runs longer than 40 rotations are cut into segments.  Used by symgpu_rotate_clifford_chain_dev (rotate.hip) above 128 terms for
+// Runs longer than 40 rotations are cut into segments.  Used by symgpu_rotate_clifford_chain_dev (rotate_driver.hip) above 128 terms for
 // rows of a power-of-two number of 16-byte chunks (<= 32); SYMGPU_CHAIN_REG=0 keeps the multi-launch forms (the tests run both).
 #include "common.h"
 #include "rotate_common.h"
@@ -187,14 +187,14 @@ __global__ __launch_bounds__(256) void k_cchain_permute(const u32x4 *__restrict_
     }
 }
 
-bool clifford_chain_registers_applicable(i64 T, int Wq) {
-    if (const char *e = getenv("SYMGPU_CHAIN_REG")) if (e[0] == '0') return false;
-    return T >= 1 && T <= ((i64)1 << CHAIN_IDX_BITS) && Wq <= 32 && (Wq & (Wq - 1)) == 0;
+bool clifford_chain_registers_applicable(i64 T, int Wq, bool chain_reg) {
+    return chain_reg && T >= 1 && T <= ((i64)1 << CHAIN_IDX_BITS) && Wq <= 32 && (Wq & (Wq - 1)) == 0;
 }
 
 // K rotations (Q rows qs_dev[K][2 Wq] on the device, ks_host[K] in 0..3) of the clean operator in `a` (T rows); `b` is a second
 // operator of the same capacity.  *in_b tells where the result ends up.
-int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u64 *qs_dev, const int *ks_host, i64 K, int *in_b) {
+constexpr int CHAIN_RETRY = 1;        // clifford_chain_registers: the one-launch sort timed out, buffers invalid, run again
+static int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u64 *qs_dev, const int *ks_host, i64 K, int *in_b) {
     hipStream_t st = ctx().stream;
     const int Wq = a->Wq;
     *in_b = 0;
@@ -222,19 +222,13 @@ int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u64 *qs_
         const u32x4 *rin = reinterpret_cast<const u32x4 *>(cur->rows), *q4 = reinterpret_cast<const u32x4 *>(qs_dev + r0 * 2 * Wq);
         u32x4 *rout = reinterpret_cast<u32x4 *>(other->rows);
         u64 *knew = kbuf[2 * (seg & 1)].as<u64>(), *ktmp = kbuf[2 * (seg & 1) + 1].as<u64>();
-#define CH_LAUNCH(WQV, NCHV) hipLaunchKernelGGL((k_cchain_reg<WQV, NCHV>), dim3(grid), dim3(256), 0, st, rin, cur->coeff, perm, T, q4, ks, n, rout, other->coeff, knew)
-#define CH_NCH(WQV) do { if (nch == 1) CH_LAUNCH(WQV, 1); else if (nch == 2) CH_LAUNCH(WQV, 2); else CH_LAUNCH(WQV, 4); } while (0)
         ProfScope *prof = new ProfScope(5);
-        switch (Wq) {
-            case 1: CH_NCH(1); break;
-            case 2: CH_NCH(2); break;
-            case 4: CH_NCH(4); break;
-            case 8: CH_NCH(8); break;
-            case 16: CH_NCH(16); break;
-            default: CH_NCH(32); break;
-        }
-#undef CH_NCH
-#undef CH_LAUNCH
+        wq_dispatch<32, 1, 2, 4, 8, 16>(Wq, [&](auto wq) {
+            wq_dispatch<4, 1, 2>(nch, [&](auto chunks) {
+                hipLaunchKernelGGL((k_cchain_reg<decltype(wq)::value, decltype(chunks)::value>), dim3(grid), dim3(256), 0, st, rin, cur->coeff, perm, T, q4, ks,
+                                   n, rout, other->coeff, knew);
+            });
+        });
         delete prof;
         KERNEL_CHECK();
         bool in_tmp = false, coop = false;
@@ -262,6 +256,18 @@ int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u64 *qs_
     // multi-launch sort
     if (timed_out) return CHAIN_RETRY;
     return SYMGPU_OK;
+}
+
+// the register chain as a form of symgpu_rotate_clifford_chain_dev; if its one-launch sort timed out at a barrier the rows in `a` / `b` are
+// garbage: restore `a` from the untouched input and run once more (the sort form is off by then, so the second run takes the multi-launch
+// radix sort)
+int chain_registers(const ChainRun &c, int *in_b) {
+    int r = clifford_chain_registers(c.a, c.b, c.T, c.qs, c.ks_host, c.K, in_b);
+    if (r != CHAIN_RETRY) return r;
+    SG_TRY(symgpu_op_copy_rows(c.a, 0, c.in, 0, c.T));
+    r = clifford_chain_registers(c.a, c.b, c.T, c.qs, c.ks_host, c.K, in_b);
+    if (r == CHAIN_RETRY) { set_error("rotate_clifford_chain: the one-launch sort timed out twice"); return SYMGPU_E_HIP; }
+    return r;
 }
 
 }  // namespace symgpu

@@ -1,0 +1,333 @@
+// rotate_driver.hip — single-Pauli rotation (reference: PauliwordOp._rotate_by_single_Pword,
+// symmer/operators/base.py:1090-1161) as ONE fused device pass over a device-resident operator.
+//
+//   R(t) P R(t)^+ = P                        if [P, Q] = 0
+//                 = cos(t) P + sin(t)(-i P Q) if {P, Q} = 0
+//
+// analyze : per row, anticommutation parity with Q and the phase exponent e of P*Q
+//           (e = (3(Y_P+Y_Q) + Y_out + 2|x_P & z_Q|) mod 4), G lanes per row, xor/popcount + shuffles.
+// scan    : positions of anticommuting rows (exclusive scan of flags).
+// build   : non-Clifford: stack [commuting | cos * anticommuting | (-i sin) i^e * (anticommuting ^ Q)] in the
+//           reference's order (base.py:1158-1161), then first-occurrence cleanup (cleanup_driver.hip) merges P^Q
+//           partners; Clifford (angle = k*pi/2): [rotated anticommuting | commuting], no merge (base.py:1139-1154);
+//           odd k: row ^ Q with c * i^e * (-i), k in {2,3}: negated (k is NOT reduced mod 4, base.py:1148).
+// Equivalent to the reference's three intermediate cleanups when the input has no duplicate rows
+// (every operator that left cleanup() qualifies).  Inputs WITH duplicate rows: the non-Clifford path
+// detects them in its hash insert and falls back to stack + cleanup; the odd-k Clifford path forms anticom_self * Q
+// through __mul__ in the reference (base.py:1143), which merges duplicate product rows and thresholds the SUMS — so an
+// operator not known to be duplicate-free (symgpu_op_s::dup_free) is checked once with the same hash insert, and if
+// duplicates exist the rotated anticommuting part goes through cleanup before the commuting rows are appended.
+//
+// This file reads the switches, plans a call and runs its stages: rotate_common.h lists the files that hold them.
+#include "rotate_common.h"
+#include <stdlib.h>
+
+namespace symgpu {
+
+// chain: the switches of a run of Clifford rotations, else those of a single rotation (the other half keeps its defaults) — every getenv
+// scans the whole environment, and the one-launch rotation is short enough for that to show
+static RotateSwitches read_rotate_switches(bool chain) {
+    RotateSwitches sw;
+    const char *e = nullptr;
+    if (!chain) {
+        sw.general = getenv("SYMGPU_ROTATE_GENERAL") != nullptr;
+        if ((e = getenv("SYMGPU_ROT_RESIDENT"))) sw.resident = e[0] == '0' ? 0 : e[0] == '2' ? 2 : e[0] == '3' ? 3 : 1;
+        if ((e = getenv("SYMGPU_ROT_HBM"))) sw.hbm = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
+    } else {
+        if ((e = getenv("SYMGPU_CHAIN_REG"))) sw.chain_reg = e[0] != '0';
+        if ((e = getenv("SYMGPU_CHAIN_LOCAL_T"))) {
+            sw.local_t_set = true;
+            sw.local_t = atoll(e);
+            if (sw.local_t > CHAIN_TMAX) sw.local_t = CHAIN_TMAX;
+        }
+        if ((e = SG_TUNE("SYMGPU_CHAIN_LDS"))) sw.chain_lds = e[0] != '0';
+        if ((e = SG_TUNE("SYMGPU_CHAIN_TWO"))) sw.chain_two = e[0] != '0';
+        if ((e = SG_TUNE("SYMGPU_CHAIN_TWO_T"))) sw.chain_two_t = atoll(e);
+    }
+    if ((e = SG_TUNE("SYMGPU_ROT_CHUNKS"))) sw.chunks = e[0] != '0';
+    if ((e = SG_TUNE("SYMGPU_ROT_ANALYZE_CAP"))) sw.analyze_cap = atoll(e);
+    return sw;
+}
+
+// The stages of one single rotation, in this order.  A stage that runs either completes the call or hands on to the next; what sends a
+// call on is found at run time (a failed verification of the one-launch kernel, duplicate rows found by the join or the check).
+struct RotationPlan {
+    bool fits_join;          // the 22-bit row index of a join-table entry holds every row
+    bool resident;           // one persistent launch (rotate_resident_try decides itself whether the operator qualifies)
+    bool join;               // non-Clifford: hash join
+    bool dup_check;          // odd-k Clifford of an operator not known to be duplicate-free: join-table insert and read-back first
+    bool clifford_fast;      // Clifford: classify, scan, write (unless the check found duplicate rows)
+    // every other call: analysis, then the general stack + cleanup
+};
+
+static RotationPlan plan_rotation(symgpu_op_t in, int clifford_k, const RotateSwitches &sw) {
+    RotationPlan pl;
+    const bool clifford = clifford_k >= 0;
+    // odd multiples of pi/2 multiply by Q through the reference's __mul__ (merge + threshold on sums): the per-row fast path is
+    // only the same thing for an operator without duplicate rows
+    const bool may_merge = clifford && (clifford_k & 1) && !in->dup_free;
+    pl.fits_join = in->T < JOIN_MAX_T;
+    pl.resident = !sw.general;
+    pl.join = !clifford && !sw.general && pl.fits_join;
+    pl.dup_check = may_merge && !sw.general && pl.fits_join;
+    pl.clifford_fast = clifford && !sw.general && in->T <= SCAN_MAX_T && (!may_merge || pl.fits_join);   // too large to check: merging path
+    return pl;
+}
+
+// The form of a run of Clifford rotations (T > 0 rows, K > 0 rotations).
+enum class ChainForm { Registers, Lds, SingleWorkgroup, TwoLaunch, FourLaunch };
+
+static ChainForm plan_chain(i64 T, int Wq, const RotateSwitches &sw) {
+    const int W = 2 * Wq;
+    const bool regs = clifford_chain_registers_applicable(T, Wq, sw.chain_reg);
+    // the whole run with the rows in registers and ONE sort of the accumulated partition bits per 40 rotations (rotate_chain.hip):
+    // faster than every other form at every size (1 term: 0.5 us per rotation against 1.6 of the LDS-resident kernel, 128 terms:
+    // 1.2 against 3.7, 10^5 terms: 5.3 against 22.9 of the two-launch form)
+    if (regs && !sw.local_t_set) return ChainForm::Registers;
+    if (sw.chain_lds && T <= sw.local_t && T <= CHAIN_LDS_T && W <= 128 && (size_t)2 * T * W * 8 <= 128 * 1024 && chain_lds_attr_ok())
+        return ChainForm::Lds;
+    if (T <= sw.local_t) return ChainForm::SingleWorkgroup;
+    if (regs) return ChainForm::Registers;        // SYMGPU_CHAIN_LOCAL_T set and T above it: the tests' way to the register chain
+    if (sw.chain_two && Wq <= 64 && (Wq & (Wq - 1)) == 0 && T <= sw.chain_two_t) return ChainForm::TwoLaunch;
+    return ChainForm::FourLaunch;
+}
+
+static int run_chain(ChainForm form, const ChainRun &c, int *in_b) {
+    switch (form) {
+        case ChainForm::Registers: return chain_registers(c, in_b);
+        case ChainForm::Lds: return chain_lds(c, in_b);
+        case ChainForm::SingleWorkgroup: return chain_single_workgroup(c, in_b);
+        case ChainForm::TwoLaunch: return chain_two_launch(c, in_b);
+        default: return chain_four_launch(c, in_b);
+    }
+}
+
+// The operator 0 * I (one identity row, coefficient 0): what the reference's cleanup() makes of an operator without terms (base.py:631-632)
+static int zero_identity_op(int Wq, symgpu_op_t *out) {
+    symgpu_op_t z = nullptr;
+    SG_TRY(symgpu_op_alloc(1, Wq, 1, &z));
+    hipStream_t st = ctx().stream;
+    hipError_t e = hipMemsetAsync(z->rows, 0, (size_t)2 * Wq * 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(z->coeff, 0, 16, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { symgpu_op_free(z); return hip_fail(e, "zero_identity_op", __FILE__, __LINE__); }
+    z->T = 1;
+    *out = z;
+    return SYMGPU_OK;
+}
+
+// does any row of `op` commute with the row q (host)?  Only asked when a non-Clifford rotation has left no term at all.
+static int any_row_commutes(symgpu_op_t op, const u64 *q_host, bool *any) {
+    symgpu_op_t q = nullptr;
+    SG_TRY(symgpu_op_upload(q_host, nullptr, 1, op->Wq, &q));
+    Scratch flags;
+    int rc = flags.alloc((size_t)op->T);
+    if (rc == SYMGPU_OK) rc = symgpu_commutes_dev(op, 0, op->T, q, flags.as<uint8_t>());
+    uint64_t sum = 0;
+    if (rc == SYMGPU_OK) rc = symgpu_dev_checksum_u8(flags.as<uint8_t>(), op->T, &sum);
+    symgpu_op_free(q);
+    *any = sum != 0;
+    return rc;
+}
+
+}  // namespace symgpu
+
+using namespace symgpu;
+
+extern "C" {
+
+int symgpu_rotate_single_dev_n(symgpu_op_t in, const uint64_t *q_row_host, double cos_t, double sin_t, int clifford_k, double thr,
+                               symgpu_op_t *out, int *all_commute, int64_t *n_out) {
+    SG_REQUIRE(n_out, "rotate_single_dev_n: null argument");
+    *n_out = 0;
+    SG_TRY(symgpu_rotate_single_dev(in, q_row_host, cos_t, sin_t, clifford_k, thr, out, all_commute));
+    if (*out) *n_out = (*out)->T;
+    return SYMGPU_OK;
+}
+
+int symgpu_rotate_single_dev(symgpu_op_t in, const uint64_t *q_row_host, double cos_t, double sin_t, int clifford_k, double thr,
+                             symgpu_op_t *out, int *all_commute) {
+    SG_ENTER(in);
+    SG_REQUIRE(in && q_row_host && out && all_commute, "rotate_single_dev: null argument");
+    SG_REQUIRE(in->coeff || in->T == 0, "rotate_single_dev: operator has no coefficients");
+    const i64 T = in->T;
+    *out = nullptr;                                                  // stages that do not complete the call leave both as they are
+    *all_commute = 1;
+    if (T == 0) return SYMGPU_OK;
+    SG_REQUIRE(T < ((i64)1 << 31), "rotate_single_dev: too many rows");
+    const RotateSwitches sw = read_rotate_switches(false);
+    const RotationPlan pl = plan_rotation(in, clifford_k, sw);
+    int done = 0;
+    if (pl.resident) {
+        SG_TRY(rotate_resident_try(in, q_row_host, cos_t, sin_t, clifford_k, thr, sw, out, all_commute, &done));
+        if (done) return SYMGPU_OK;
+    }
+    RotationRun r{in, q_row_host, cos_t, sin_t, thr, clifford_k, sw, out, all_commute};
+    SG_TRY(r.q.alloc((size_t)2 * in->Wq * 8));
+    SG_TRY(r.anti.alloc((size_t)T * 4));
+    SG_TRY(r.ph.alloc((size_t)T));
+    // exactly one analysis launch; Q reaches the device with it (in its kernel arguments when the row has <= 64 words)
+    if (pl.join) {
+        SG_TRY(rotate_join(r, &done));
+        if (done) return SYMGPU_OK;                                  // else duplicate rows: the general stage
+    } else if (pl.dup_check) {
+        SG_TRY(rotate_dup_check(r));
+    } else {
+        SG_TRY(analyze_rows(in, r.q.as<u64>(), r.anti.as<u32>(), r.ph.as<uint8_t>(), nullptr, sw, q_row_host));
+    }
+    if (pl.clifford_fast && !r.has_dup) return rotate_clifford_fast(r);
+    return rotate_general(r);
+}
+
+int symgpu_perform_rotations_dev(symgpu_op_t in, const uint64_t *q_rows_host, const double *cos_t, const double *sin_t, const int *ks_host, int64_t K,
+                                 double thr, int clean, symgpu_op_t *out, uint8_t *acted, int64_t *n_done, int *clean_out) {
+    SG_ENTER(in);
+    SG_REQUIRE(in && out && n_done && clean_out && K >= 0 && (K == 0 || (q_rows_host && cos_t && sin_t && ks_host)), "perform_rotations_dev: null argument");
+    const int W = 2 * in->Wq;
+    symgpu_op_t cur = in;                                            // borrowed while cur == in, owned otherwise
+    auto replace = [&](symgpu_op_t next) { if (cur != in) symgpu_op_free(cur); cur = next; };
+    *out = nullptr;
+    i64 step = 0;
+    int rc = SYMGPU_OK;
+    while (step < K && rc == SYMGPU_OK) {
+        if (cur->T == 0) {
+            // every rotation is the identity on an operator without terms (np.all of an empty mask, base.py:1130-1133) and the
+            // cleanup() that follows it returns 0 * I (base.py:631-632); the next step's cleanup() drops that term again
+            symgpu_op_t z = nullptr;
+            rc = zero_identity_op(in->Wq, &z);
+            if (rc != SYMGPU_OK) break;
+            replace(z);
+            clean = 0;
+            ++step;
+            continue;
+        }
+        if (clean && cur->T <= ((i64)1 << 22) && ks_host[step] >= 0) {
+            // a run of Clifford rotations of a clean operator: no step drops or merges anything, so the reference's per-step cleanup()
+            // is the identity and the whole run goes to the chain entry point
+            i64 e = step;
+            while (e < K && ks_host[e] >= 0) ++e;
+            symgpu_op_t res = nullptr;
+            rc = symgpu_rotate_clifford_chain_dev(cur, q_rows_host + step * W, ks_host + step, e - step, &res);
+            if (rc != SYMGPU_OK) break;
+            replace(res);
+            step = e;
+            continue;
+        }
+        symgpu_op_t res = nullptr;
+        int allc = 1;
+        rc = symgpu_rotate_single_dev(cur, q_rows_host + step * W, cos_t[step], sin_t[step], ks_host[step], thr, &res, &allc);
+        if (rc != SYMGPU_OK) break;
+        if (!allc && res && res->T == 0) {
+            // The rotation itself has left no term.  Clifford: the rows are vstack([cleaned product, commuting rows]) = none, and the
+            // cleanup() after it gives 0 * I.  Non-Clifford: the result is `commute_self + anticom_part` (base.py:1159-1161), an
+            // append + cleanup that yields 0 * I when BOTH parts hold no row (then the loop's cleanup() drops its term: no terms) and
+            // an operator without terms when commuting rows cancelled each other (then the loop's cleanup() gives 0 * I).
+            bool zero_identity = true;
+            if (ks_host[step] < 0) {
+                bool any = false;
+                rc = any_row_commutes(cur, q_rows_host + step * W, &any);
+                if (rc != SYMGPU_OK) { symgpu_op_free(res); break; }
+                zero_identity = any;
+            }
+            if (acted) acted[step] = 1;
+            if (zero_identity) {
+                symgpu_op_free(res);
+                res = nullptr;
+                rc = zero_identity_op(in->Wq, &res);
+                if (rc != SYMGPU_OK) break;
+                clean = 0;
+            } else {
+                clean = 1;                                          // no terms, and the cleanup() of this step has been applied
+            }
+            replace(res);
+            ++step;
+            continue;
+        }
+        if (!allc) { if (acted) acted[step] = 1; replace(res); }
+        else if (res) symgpu_op_free(res);
+        ++step;
+        if (!clean) {
+            symgpu_op_t cleaned = nullptr;
+            rc = symgpu_cleanup_dev(cur, thr, 1, &cleaned);          // may leave no term (0 * I, or X + (-X) after an even multiple of pi/2)
+            if (rc != SYMGPU_OK) break;
+            replace(cleaned);
+            clean = 1;
+        }
+    }
+    if (rc != SYMGPU_OK) { if (cur != in) symgpu_op_free(cur); return rc; }
+    *n_done = step;
+    *clean_out = clean;
+    *out = cur != in ? cur : nullptr;                                // nullptr: the operator is unchanged, keep using `in`
+    return SYMGPU_OK;
+}
+
+int symgpu_debug_rotation_trace(uint64_t *out, int max_workgroups, int *n_workgroups) {
+    SG_TRY(require_ctx());
+    SG_REQUIRE(out && n_workgroups && max_workgroups >= 0, "debug_rotation_trace");
+    return rotate_resident_trace(out, max_workgroups, n_workgroups);
+}
+
+int symgpu_rotate_single(const uint64_t *rows, const double *coeff, int64_t N, int Wq, const uint64_t *q_row, double cos_t, double sin_t,
+                         int clifford_k, double thr, uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out,
+                         int *all_commute) {
+    SG_TRY(require_ctx());
+    SG_REQUIRE(N >= 0 && Wq >= 1 && q_row && all_commute && n_out, "rotate_single: arguments");
+    SG_REQUIRE(N == 0 || (rows && coeff), "rotate_single: null input");
+    symgpu_op_t in = nullptr, res = nullptr;
+    SG_TRY(symgpu_op_upload(rows, coeff, N, Wq, &in));
+    int rc = symgpu_rotate_single_dev(in, q_row, cos_t, sin_t, clifford_k, thr, &res, all_commute);
+    symgpu_op_free(in);
+    if (rc != SYMGPU_OK) return rc;
+    if (*all_commute || !res) { *n_out = N; if (res) symgpu_op_free(res); return SYMGPU_OK; }
+    *n_out = res->T;
+    if (res->T > capacity) {
+        set_error("rotate_single: capacity %lld < %lld rows", (long long)capacity, (long long)res->T);
+        rc = SYMGPU_E_CAPACITY;
+    } else {
+        rc = symgpu_op_download(res, out_rows, out_coeff, capacity);
+    }
+    symgpu_op_free(res);
+    return rc;
+}
+
+int symgpu_rotate_clifford_chain_dev(symgpu_op_t in, const uint64_t *q_rows_host, const int *ks_host, int64_t K, symgpu_op_t *out) {
+    SG_ENTER(in);
+    SG_REQUIRE(in && out && K >= 0 && (K == 0 || (q_rows_host && ks_host)), "rotate_clifford_chain_dev: null argument");
+    SG_REQUIRE(in->coeff || in->T == 0, "rotate_clifford_chain_dev: operator has no coefficients");
+    SG_REQUIRE(in->dup_free, "rotate_clifford_chain_dev: the operator must come from a cleanup (no duplicate rows, |c| > threshold)");
+    SG_REQUIRE(in->T <= ((i64)1 << 22), "rotate_clifford_chain_dev: more than 2^22 rows (rotate one by one)");
+    for (i64 r = 0; r < K; ++r) SG_REQUIRE(ks_host[r] >= 0 && ks_host[r] <= 3, "rotate_clifford_chain_dev: k must be 0..3 (see rotation_args)");
+    hipStream_t st = ctx().stream;
+    const i64 T = in->T;
+    const int Wq = in->Wq, W = 2 * Wq;
+    *out = nullptr;
+    const RotateSwitches sw = read_rotate_switches(true);
+    symgpu_op_t a = nullptr, b = nullptr;
+    SG_TRY(symgpu_op_alloc(T > 0 ? T : 1, Wq, 1, &a));
+    int rc = symgpu_op_alloc(T > 0 ? T : 1, Wq, 1, &b);
+    if (rc == SYMGPU_OK) rc = symgpu_op_copy_rows(a, 0, in, 0, T);
+    Scratch qs, ks;
+    int in_b = 0;
+    if (rc == SYMGPU_OK && T > 0 && K > 0) {
+        rc = qs.alloc((size_t)K * W * 8);
+        if (rc == SYMGPU_OK) rc = ks.alloc((size_t)K * 4);
+        hipError_t e = hipSuccess;
+        if (rc == SYMGPU_OK) e = hipMemcpyAsync(qs.p, q_rows_host, (size_t)K * W * 8, hipMemcpyHostToDevice, st);
+        if (rc == SYMGPU_OK && e == hipSuccess) e = hipMemcpyAsync(ks.p, ks_host, (size_t)K * 4, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) rc = hip_fail(e, "rotate_clifford_chain_dev", __FILE__, __LINE__);
+        const ChainRun c{in, a, b, T, K, Wq, qs.as<u64>(), ks.as<int>(), ks_host, sw};
+        if (rc == SYMGPU_OK) rc = run_chain(plan_chain(T, Wq, sw), c, &in_b);          // returns with the stream synchronised
+    } else if (rc == SYMGPU_OK) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = hip_fail(e, "rotate_clifford_chain_dev", __FILE__, __LINE__);
+    }
+    if (rc != SYMGPU_OK) { symgpu_op_free(a); symgpu_op_free(b); return rc; }
+    symgpu_op_t res = in_b ? b : a;
+    symgpu_op_free(in_b ? a : b);
+    res->T = T;
+    res->dup_free = 1;                                              // a permutation of distinct rows XORed with Q on a Q-anticommuting subset
+    *out = res;
+    return SYMGPU_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // rotate_resident.hip — a single-Pauli rotation (reference: PauliwordOp._rotate_by_single_Pword, symmer/operators/base.py:1090-1161)
 // as ONE persistent launch.
 //
-// The multi-launch paths of rotate.hip (analyze | match | scan | write) are bound by their three kernel boundaries, by the second
+// The multi-launch paths (rotate_analyze.hip, rotate_fast.hip: analyze | match | scan | write) are bound by their three kernel boundaries, by the second
 // pass over the rows and by the host round trips between them, not by bytes: 40 us of kernels for 8.5 us of traffic at 10^5 terms of
 // 1,000 qubits.  Here the operator is spread over the chip instead: one workgroup per CU, each owning a contiguous block of
 // ceil(T / G) rows that it reads from HBM ONCE into its LDS (256 CUs x <= 150 KiB = 38 MB of operator; BASELINE cfg2 is 25.6 MB),
@@ -20,7 +20,7 @@
 //   g2  all-gather #2: kept anticommuting / new rows per workgroup; the commuting rows are written while it is in flight
 //   C   rows (LDS -> HBM, 16 bytes per lane), coefficients and handed-on hashes to their final slots; counts to pinned host memory
 //
-// Output order, sums and thresholds are those of rotate.hip's hash-join path (commuting | cos * anticommuting (+ partner) | new rows,
+// Output order, sums and thresholds are those of the hash-join path (rotate_fast.hip) (commuting | cos * anticommuting (+ partner) | new rows,
 // strict |c| > thr; Clifford: rotated anticommuting | commuting), bit for bit — tests/test_gpu_parity.py runs both.
 // Exactness does not rest on the hash: the second row of every pair is compared with its partner chunk by chunk (row ^ Q against
 // the partner's row in HBM); a mismatch, a third row under one canonical key, or an all-gather that does not complete (workgroups
@@ -176,7 +176,7 @@ __device__ __forceinline__ f64x2 plus_zero(f64x2 c) { return f64x2{__dadd_rn(0.0
 __device__ __forceinline__ void row_store(u32x4 v, u32x4 *p) { __builtin_nontemporal_store(v, p); }
 #define RES_STAMP(i) do { if (a.trace && tid == 0) a.trace[(size_t)w * 16 + (i)] = wall_clock64(); } while (0)
 
-// flag and the two phase exponents of a row from its counts (rotate.hip: k_rot_analyze): bit 0 = anticommutes with Q, bits 1-2 = the
+// flag and the two phase exponents of a row from its counts (k_rot_analyze, rotate_analyze.hip): bit 0 = anticommutes with Q, bits 1-2 = the
 // exponent e of P * Q, bits 3-4 = the exponent e' of (P ^ Q) * Q, i.e. the e of the row's partner
 __device__ __forceinline__ uint8_t res_info(u32 anti, u32 fp, u32 yp, u32 yout, u32 yq) {
     const u32 e = (3u * (yp + yq) + yout + 2u * fp) & 3u;
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
             s_cls[r] = cls;
         }
     } else {
-        // ---- Clifford: class and rotated coefficient per row (k_rotc_classify of rotate.hip) -----------------------------------
+        // ---- Clifford: class and rotated coefficient per row (k_rotc_classify, rotate_fast.hip) -----------------------------------
         const int k = a.k;
         for (int r = tid; r < Rw; r += RES_THREADS) {
             const uint8_t info = s_info[r];
@@ -635,11 +635,8 @@ __global__ __launch_bounds__(RES_THREADS) void k_rot_resident(const ResArgs a) {
 
 typedef void (*ResKernel)(const ResArgs);
 static ResKernel res_kernel(bool clifford, int Wq) {
-#define RES_PICK(M) \
-    switch (Wq) { case 1: return k_rot_resident<M, 1>; case 2: return k_rot_resident<M, 2>; case 4: return k_rot_resident<M, 4>; case 8: return k_rot_resident<M, 8>; \
-                  case 16: return k_rot_resident<M, 16>; case 32: return k_rot_resident<M, 32>; default: return k_rot_resident<M, 0>; }
-    if (clifford) { RES_PICK(1) } else { RES_PICK(0) }
-#undef RES_PICK
+    if (clifford) return wq_dispatch<0, 1, 2, 4, 8, 16, 32>(Wq, [](auto wq) -> ResKernel { return k_rot_resident<1, decltype(wq)::value>; });
+    return wq_dispatch<0, 1, 2, 4, 8, 16, 32>(Wq, [](auto wq) -> ResKernel { return k_rot_resident<0, decltype(wq)::value>; });
 }
 
 static u64 *g_res_trace = nullptr;
@@ -654,19 +651,17 @@ int rotate_resident_trace(u64 *out, int max_wgs, int *n_wgs) {
     return SYMGPU_OK;
 }
 
-int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double sin_t, int clifford_k, double thr, symgpu_op_t *out,
-                        int *all_commute, int *done) {
+int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double sin_t, int clifford_k, double thr, const RotateSwitches &sw,
+                        symgpu_op_t *out, int *all_commute, int *done) {
     *done = 0;
     Context &c = ctx();
     const i64 t_enter = host_ns();
-    if (const char *e = getenv("SYMGPU_ROT_RESIDENT")) {                          // read on every call: 0 = off, 2 = on again after a failure, 3 = tests: inject a time-out
-        if (e[0] == '0') return SYMGPU_OK;
-        if (e[0] == '2') c.res_disabled = false;
-    }
+    if (sw.resident == 0) return SYMGPU_OK;
+    if (sw.resident == 2) c.res_disabled = false;
     if (c.res_disabled) return SYMGPU_OK;
     const i64 T = in->T;
     const int Wq = in->Wq, W = 2 * Wq;
-    if (T < 1 || W > RES_MAX_W || T >= ((i64)1 << 22) - 1) return SYMGPU_OK;
+    if (T < 1 || W > RES_MAX_W || T >= JOIN_MAX_T) return SYMGPU_OK;
     const bool clifford = clifford_k >= 0;
     if ((!clifford || (clifford_k & 1)) && !in->dup_free) return SYMGPU_OK;      // merges possible: the multi-launch paths check / handle them
     bool have_hash = in->hash && c.hash_tab && in->hash_seed == c.hash_seed;
@@ -685,8 +680,7 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
     if ((size_t)L.total > RES_LDS_MAX && pow2) { nreg = 2; L = res_layout((int)R, Wq, nreg); }
     // beyond that (round 6): only the 26 bytes per row stay on the chip, the rows are read a second
     // time when they are written out — 1e5 terms of 2,000 qubits (51 MB): 73 us on the multi-launch path, see DESIGN 3.4
-    const char *hbm_env = getenv("SYMGPU_ROT_HBM");                                  // 0: off; 2 (tests): also for operators that would fit the chip
-    if (((size_t)L.total > RES_LDS_MAX && !(hbm_env && hbm_env[0] == '0')) || (hbm_env && hbm_env[0] == '2')) { nreg = 0; hbm = 1; L = res_layout((int)R, Wq, 0, 1); }
+    if (((size_t)L.total > RES_LDS_MAX && sw.hbm != 0) || sw.hbm == 2) { nreg = 0; hbm = 1; L = res_layout((int)R, Wq, 0, 1); }
     if ((size_t)L.total > RES_LDS_MAX) return SYMGPU_OK;
     const bool attr_ok = SG_DEVICE_ONCE(([] {
         for (int m = 0; m < 2; ++m)
@@ -765,7 +759,7 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
     a.finished = a.fail + 2; a.finish_target = finished_base + (u32)G;
     finished_base += (u32)G;
     a.epoch = c.res_epoch;
-    { const char *e = getenv("SYMGPU_ROT_RESIDENT"); a.inject = (e && e[0] == '3') ? 1 : 0; }                      // 3 = tests: the kernel reports a failed verification
+    a.inject = sw.resident == 3 ? 1 : 0;                                          // tests: the kernel reports a failed verification
     a.trace = nullptr;
     if (const char *e = SG_TUNE("SYMGPU_RES_TRACE")) if (e[0] == '1') {
         if (!g_res_trace) { HIP_TRY(hipMalloc((void **)&g_res_trace, (size_t)RES_MAX_WG * 16 * 8)); }

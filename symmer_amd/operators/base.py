@@ -629,7 +629,7 @@ class PauliwordOp:
     def _rotate_by_single_Pword(self, Pword: "PauliwordOp", angle: float = None, threshold: float = 1e-18
                                 ) -> "PauliwordOp":
         """base.py:1090-1161 as one fused device pass; ``threshold`` decides Clifford vs non-Clifford as in base.py:1146.
-        Operators with duplicate rows are detected on the device and take the merging path (``csrc/rotate.hip``)."""
+        Operators with duplicate rows are detected on the device and take the merging path (``csrc/rotate_driver.hip``)."""
         if angle is None:
             angle = np.pi / 2
         if angle.imag != 0:

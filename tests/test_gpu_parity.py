@@ -1336,7 +1336,7 @@ def test_wide_rows_word_parallel_path(n, N, M, force, monkeypatch):
 @pytest.mark.parametrize('n,T', [(524288 + 77, 6), (600000, 3)])
 def test_very_long_rows_segment_parallel_hash(n, T):
     """Rows of >= 8192 words take the segment-parallel row hash (k_hash_rows_long); it must be the SAME function as the Horner
-    scheme of k_hash_rows, the host's host_row_hash (a rotation's Q row) and rotate.hip's in-kernel hash: cleanup merges duplicates,
+    scheme of k_hash_rows, the host's host_row_hash (a rotation's Q row) and the rotation's in-kernel hash (rotate_analyze.hip): cleanup merges duplicates,
     and a rotation merges P with (P Q) Q — rows hashed by different implementations — exactly like the oracle."""
     rng = np.random.default_rng(1300 + T)
     S = rng.random((T, 2 * n)) < 0.3
