@@ -10,11 +10,16 @@ GPU).  One "step" = (N>1: RCCL all-gather of the packed right operand over xGMI,
 full product of this rank's left block against the whole right operand.  Inputs are resident in HBM before the
 timed region.  Weak scaling: per-GPU work is fixed, value = all ranks' pairs / max-over-ranks time.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line.  Everything else it can
+measure runs only with --full: `cpu_baseline`, `extras`, the `api` objects of the other workloads, the isolated row-kernel and
+HBM-probe figures of the product's `roofline`, `strong_scaling` (N>1) and the rotation workload's Clifford and saturated-chain legs.
+
 roofline     — dominant kernel k_mul_rows_e (HBM-write stream of the product rows, which also leaves one phase byte per
                pair): algorithmic bytes 16*Wq per pair (256 B at n=1000) x pairs per launch / average launch duration
                from HIP events recorded around every launch in the timed region (library stream).  A second streaming
                kernel (k_mul_coeff_expand) turns the phase bytes into the 16 B/pair coefficients right after it; the
-               whole step moves 16*Wq+16 B/pair (`whole_step_GBps`).  peak = 8 TB/s (MI355X_MICROARCH.md).
+               whole step moves 16*Wq+16 B/pair (`whole_step_GBps`).  peak = 8 TB/s (MI355X_MICROARCH.md).  --full adds the
+               plain row stream timed on its own (`isolated_*`) and the library's fill / copy probe (`*_probe_GBps`).
 cpu_baseline — the NumPy restatement of the reference algorithm (oracle/oracle_np.py: broadcast XOR on
                1-byte-per-bit matrices, per-bit popcount sums, complex outer product; base.py:783-792) timed on a
                bounded sample of the same workload on the host cores.
@@ -65,12 +70,16 @@ def parse():
     ap.add_argument('--adj-terms', type=int, default=200000)
     ap.add_argument('--adj-qubits', type=int, default=2000)
     ap.add_argument('--adj-slab-rows', type=int, default=0, help='adjacency: rows per launch / output slab (0: as many as a quarter of the free HBM holds)')
-    ap.add_argument('--no-extras', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the CPU baselines, the `api` objects, the other BASELINE configs '
+                         '(`extras`), the isolated row-kernel and HBM-probe figures, strong scaling (--gpus > 1), the rotation workload\'s Clifford '
+                         'and saturated-chain legs.  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip `extras` (and the rotation workload\'s Clifford / saturated-chain legs)')
     ap.add_argument('--single-process', action='store_true', help='drive all --gpus devices from THIS process (symgpu_init_all + grouped RCCL all-gather); '
                     'the default whenever --gpus > 1 and no launcher has set WORLD_SIZE')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-api', action='store_true', help='skip the `api` objects (the reference\'s call spelling timed on the drop-in classes)')
-    ap.add_argument('--cpu-full', action='store_true', help='gf2: time the CPU restatement on the full 4000 x 54000 matrix (~70 s) instead of citing the cached run')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-api', action='store_true', help='with --full: skip the `api` objects (the reference\'s call spelling timed on the drop-in classes)')
+    ap.add_argument('--cpu-full', action='store_true', help='gf2 with --full: time the CPU restatement on the full 4000 x 54000 matrix (~70 s) instead of citing the cached run')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='product workload: after the timed steps, write what the last step computed (a fixed, seeded sample of the product rows of '
                          'its last output slab, with their coefficients and pair indices) as DIR/<name>.npy, float64, at most 64 MB (rank 0)')
@@ -82,7 +91,9 @@ def parse():
     if args.dump_outputs is not None and (args.single_process or (args.gpus > 1 and 'WORLD_SIZE' not in os.environ)):
         ap.error('--dump-outputs is implemented for one process per GPU (the default with --gpus 1 or under a launcher)')
     if os.environ.get('BENCH_CPU_FULL', '0') == '1':
-        args.cpu_full = True                                      # the driver passes no flags: the environment switches the full-size CPU leg on
+        args.cpu_full = True                                      # the environment switches the full-size CPU leg on (it runs with --full)
+    if not args.full:
+        args.no_extras = args.no_cpu = args.no_api = True         # a plain run: only what the contract line needs
     # a millisecond-scale step needs more than three of them for a stable figure (clocks, allocator): mul_cleanup 20 + 3, gf2 10 + 2
     d_steps, d_warm = {'mul_cleanup': (20, 3), 'gf2': (10, 2)}.get(args.workload, (3, 1))
     if args.steps is None: args.steps = d_steps
@@ -220,7 +231,7 @@ def main():
         out['degraded'] = comm.degraded          # top-level flag: the all-gather did not run over RCCL/xGMI
     # the plain row stream k_mul_rows (rows-only output slab: no phase bytes, no coefficients), outside the timed region: four warm
     # launches (a fresh 6.5 GB slab: first touch), then the best of three batches of eight
-    if rank == 0:
+    if rank == 0 and args.full:
         rows_only = DeviceOp.alloc(slab * Ni, wq, with_coeff=False)
         o1 = min(M, slab)
         for _ in range(4):
@@ -243,7 +254,7 @@ def main():
         rows_only.free()
     # the library's own one-shot 16-byte fill / copy over 4 GiB buffers: a PROBE of the box, not a ceiling (the row stream's
     # one-row-per-block write pattern beats the probe's grid-stride fill)
-    if rank == 0:
+    if rank == 0 and args.full:
         fill, cp = ctypes.c_double(0), ctypes.c_double(0)
         _lib.check(lib.symgpu_membw_probe(4 << 30, ctypes.addressof(fill), ctypes.addressof(cp)))
         out['roofline']['fill_probe_GBps'] = fill.value
@@ -255,7 +266,7 @@ def main():
                          {'n_qubits': n, 'left_terms_per_gpu': Ni, 'right_terms': M, 'slab_rows': slab})
     # STRONG scaling next to the weak line (world > 1): the same 10^5 x 10^5 product with the LEFT axis split over the ranks — 1/world of the
     # left terms per GPU, world x as many outer rows per output slab, so that a launch still writes the same ~6.5 GB.
-    if world > 1:
+    if world > 1 and args.full:
         try:
             ni_s = (Ni + world - 1) // world
             left_s = DeviceOp.random(ni_s, n, 0.3, seed=4321 + 7919 * rank)

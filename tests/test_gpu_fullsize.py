@@ -556,6 +556,36 @@ def test_bench_line_schema_small_workload():
     assert len(json.dumps(sm)) < 1500
 
 
+def test_bench_isolated_and_probe_figures_run_with_full_only():
+    """The product line's own extra legs (the row stream timed on its own, the fill / copy probe) run with `--full` and not in a plain run;
+    the contract keys are the same in both."""
+    import json, sys, io, contextlib, importlib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module('bench')
+    docs = {}
+    for full in (False, True):
+        argv, buf = sys.argv, io.StringIO()
+        sys.argv = ['bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--left-terms', '4000', '--right-terms', '3000', '--qubits', '200',
+                    '--no-extras', '--no-cpu'] + (['--full'] if full else [])
+        try:
+            with contextlib.redirect_stdout(buf):                  # in-process: no exec from a process that holds the GPU
+                bench.main()
+        finally:
+            sys.argv = argv
+        lines = [l for l in buf.getvalue().splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        docs[full] = json.loads(lines[0])
+    plain, full = docs[False], docs[True]
+    extra = ('isolated_GBps', 'isolated_frac', 'isolated_avg_launch_ms', 'fill_probe_GBps', 'copy_probe_GBps')
+    assert not any(k in plain['roofline'] for k in extra) and 'extras' not in plain and 'cpu_baseline' not in plain
+    assert all(k in full['roofline'] for k in extra) and full['roofline']['isolated_GBps'] > 0 and full['roofline']['fill_probe_GBps'] > 0
+    for key in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'warmup', 'config'):
+        assert plain[key] == full[key], key
+    assert plain['value'] > 0 and plain['ms_per_step'] > 0 and plain['roofline']['launches'] == full['roofline']['launches']
+
+
 def test_bench_adjacency_workload_schema():
     """`bench.py --workload adjacency` (BASELINE cfg5 shape, reduced): one JSON line, strong scaling, T*T pairs per step."""
     import json, sys, io, contextlib, importlib

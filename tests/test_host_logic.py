@@ -294,6 +294,28 @@ def test_bench_summary_carries_every_config():
     assert sm['cfg5_adjacency']['predicted_8gpu_x'] == 7.43 and sm['cfg3_mul_cleanup']['api'] == [0.002346, 0.1654] and sm['failed_sections'] == ['broken_section']
 
 
+def test_bench_plain_run_leaves_the_other_measurements_to_full(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures its contract line only: the CPU baselines, the `api` objects and `extras`
+    run with `--full`, where `--no-cpu` / `--no-api` / `--no-extras` still switch them off one by one; steps and warm-up are untouched."""
+    import sys, importlib
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    bench = importlib.import_module('bench')
+    monkeypatch.delenv('BENCH_CPU_FULL', raising=False)
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', *argv])
+        return bench.parse()
+    a = parse('--gpus', '1', '--steps', '5', '--warmup', '2')
+    assert not a.full and a.no_cpu and a.no_api and a.no_extras and (a.steps, a.warmup) == (5, 2)
+    a = parse('--gpus', '1', '--steps', '5', '--warmup', '2', '--full')
+    assert a.full and not (a.no_cpu or a.no_api or a.no_extras) and (a.steps, a.warmup) == (5, 2)
+    a = parse('--full', '--no-cpu', '--workload', 'gf2')
+    assert a.no_cpu and not (a.no_api or a.no_extras) and (a.steps, a.warmup) == (10, 2)
+    a = parse('--workload', 'rotation')
+    assert a.no_cpu and a.no_api and a.no_extras and (a.steps, a.warmup) == (3, 1)
+
+
 def test_lexicographic_order_from_packed_rows_equals_numpy_lexsort_of_the_columns():
     """``sort('lex')`` and ``==`` (base.py:455-492, 640-662) order the rows by ``np.lexsort(symp_matrix.T)`` (last column = primary key); the
     drop-in takes the order from the packed rows — 2 Wq sort keys instead of 2n — which must be the SAME permutation, ties included."""

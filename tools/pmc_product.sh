@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 tag=${1:-r05}
 out=gpurun_out/$tag; rm -rf $out; mkdir -p $out
-cmd="bench.py --steps 2 --warmup 1 --no-extras --no-cpu"
+cmd="bench.py --steps 2 --warmup 1 --full --no-extras --no-cpu"          # --full: the 4 GiB copy probe is the calibration below
 timeout 900 rocprofv3 --pmc WRITE_SIZE -d $out/w -o w -- python3 $cmd > $out/w.log 2>&1
 timeout 900 rocprofv3 --pmc FETCH_SIZE -d $out/r -o r -- python3 $cmd > $out/r.log 2>&1
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/t -o t -- python3 $cmd > $out/${tag}_bench_n1_under_rocprof.json 2> $out/t.log
@@ -25,7 +25,7 @@ _, cr = per_launch(f'{out}/r/r_results.db', 'FETCH_SIZE', '%k_probe_copy%')
 line = [l for l in open(f'{out}/{tag}_bench_n1_under_rocprof.json') if l.startswith('{')][-1]
 cfg = json.loads(line)['config']
 doc = {
-    'source': f'rocprofv3 --pmc WRITE_SIZE / --pmc FETCH_SIZE (separate passes) on `python3 bench.py --steps 2 --warmup 1 --no-extras --no-cpu`, MI355X; summaries in profiles/{tag}_product_pmc.txt (tools/pmc_product.sh)',
+    'source': f'rocprofv3 --pmc WRITE_SIZE / --pmc FETCH_SIZE (separate passes) on `python3 bench.py --steps 2 --warmup 1 --full --no-extras --no-cpu`, MI355X; summaries in profiles/{tag}_product_pmc.txt (tools/pmc_product.sh)',
     'config': {'n_qubits': cfg['n_qubits'], 'left_terms_per_gpu': cfg['left_terms_per_gpu'], 'right_terms': cfg['right_terms'], 'slab_rows': cfg['slab_rows']},
     'kernel': 'k_mul_rows_e', 'launches_profiled': nw,
     'kernel_source_sha256': hashlib.sha256(open('symmer_amd/csrc/product.hip', 'rb').read()).hexdigest(),

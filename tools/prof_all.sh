@@ -23,9 +23,9 @@ timeout 600 rocprofv3 --kernel-trace --stats -d $dst/chain -o t -- python3 tools
 rm -rf $dst/adj $dst/adjpmc $dst/adjpmc2 $dst/chain
 # the traffic JSONs of THIS source go where bench.py looks for them (on the box's copy of the tree), then:
 cp $dst/${tag}_*traffic.json profiles/ 2>/dev/null
-# 5. the bench lines as the driver would see them (un-profiled; their `traffic` comes from the JSONs just written)
-timeout 900 python3 bench.py > $dst/${tag}_bench_n1.json 2> $dst/bench_n1.err
+# 5. the full bench lines (un-profiled, --full: CPU baselines, api objects, extras; their `traffic` comes from the JSONs just written)
+timeout 900 python3 bench.py --full > $dst/${tag}_bench_n1.json 2> $dst/bench_n1.err
 for wl in rotation mul_cleanup gf2 adjacency; do
-  timeout 900 python3 bench.py --workload $wl > $dst/${tag}_${wl}_n1.json 2> $dst/${wl}_n1.err
+  timeout 900 python3 bench.py --workload $wl --full > $dst/${tag}_${wl}_n1.json 2> $dst/${wl}_n1.err
 done
 ls -la $dst | head -50
