@@ -16,9 +16,11 @@
 //    number of 16-byte chunks: n in 65..128, 193..256, 449..512, 961..1024, 1985..2048, 4033..4096, or n <= 64) — the row
 //    stream has its VALU idle, and in the row-major layout the X and the Z words of a term sit in the two halves of an aligned
 //    lane group: the phase sum  Y_out + 2|x_left & z_right|  of every output row is formed on the way (DPP lane exchange,
-//    v_bcnt, three DPP adds: measured free, tools/ubench_fused.hip) and leaves as ONE byte per pair; a purely streaming second
-//    kernel expands bytes to coefficients at HBM speed.  The word-major VALU-bound k_mul_coeff (0.158 ms per 2.56e7 pairs)
-//    is replaced by 0.075 ms of streaming: 1.083 -> 1.0 ms per slab.
+//    v_bcnt, three DPP adds: measured free, tools/ubench_fused.hip) and leaves as 2 bits per pair, four pairs to a byte; a purely
+//    streaming second kernel expands them to coefficients.  The word-major VALU-bound k_mul_coeff (0.158 ms per 2.56e7 pairs)
+//    is replaced by 0.075 ms of streaming: 1.083 -> 1.0 ms per slab.  The expansion writes like the row stream: one contiguous
+//    4 KiB piece of one outer row per workgroup, dispatch order = address order, grid.x a multiple of 8: 409.6 MB of
+//    coefficients per 256-row slab at n = 1000 in 66 us = 6.2 TB/s (four outer rows per workgroup: 81 us).
 #include "common.h"
 #include <stdlib.h>
 #include <stdio.h>
@@ -273,15 +275,17 @@ template <int WQ> __device__ __forceinline__ u32 half_row_sum(u32 s) {
     return s;
 }
 
-// One output row segment per block (the sequential write pattern of k_mul_rows<1, true>, rto = 1) plus, per output row, the byte
-// (Y_out + 2 |x_left & z_right|) mod 4.  The 256/WQ bytes of a block are gathered in LDS and leave as one store of wave 0.
-// e-byte index: o * gx * R + ((bx % 8) * (gx / 8) + bx / 8) * R + row in block, R = 256 / WQ: workgroups go to the XCDs round
-// robin, so the bytes of consecutive blocks OF ONE XCD are adjacent and fill whole lines in that XCD's L2 (plain stores) —
-// bytes of neighbouring blocks interleaved from 8 different L2s cost partial-line write-backs.
+// One output row segment per block (the sequential write pattern of k_mul_rows<1, true>, rto = 1) plus, per output row, the 2-bit
+// phase sum (Y_out + 2 |x_left & z_right|) mod 4, four rows to a byte (row 4k + j in bits 2j, 2j + 1).  The R = 256/WQ sums of a block
+// are gathered in LDS and leave as R/4 bytes (4 at WQ = 16, 1 at WQ = 64) stored by the first lanes of wave 0.
+// Byte index: (o * gx + (bx % 8) * (gx / 8) + bx / 8) * R/4 + row in block / 4: workgroups go to the XCDs round robin, so the bytes
+// of consecutive blocks OF ONE XCD are adjacent and fill whole lines in that XCD's L2 (plain stores) — bytes of neighbouring blocks
+// interleaved from 8 different L2s cost partial-line write-backs.
 template <int WQ, bool INNER_LEFT>
 __global__ __launch_bounds__(256) void k_mul_rows_e(const u32x4 *__restrict__ inner, i64 n_chunks, const u32x4 *__restrict__ outer,
                                                      u32x4 *__restrict__ out, unsigned char *__restrict__ eb, i64 out_stride) {
     constexpr int R = 256 / WQ;
+    static_assert(R % 4 == 0, "four row sums per byte: WQ <= 64");
     __shared__ __attribute__((aligned(16))) unsigned char sb[R];
     const i64 cb = (i64)blockIdx.x * 256;
     if (cb >= n_chunks) return;                                      // surplus block of the padded grid
@@ -313,49 +317,35 @@ __global__ __launch_bounds__(256) void k_mul_rows_e(const u32x4 *__restrict__ in
     if ((threadIdx.x & (WQ - 1)) == (INNER_LEFT ? 0 : WQ / 2)) sb[threadIdx.x / WQ] = (unsigned char)(s & 3u);
     __syncthreads();
     if (threadIdx.x < R / 4) {
+        const u32 q = reinterpret_cast<const u32 *>(sb)[threadIdx.x];      // the sums of rows 4t .. 4t + 3, one per byte
         const i64 gx = gridDim.x;
-        unsigned char *dst = eb + (o * gx + (i64)(blockIdx.x & 7) * (gx >> 3) + (i64)(blockIdx.x >> 3)) * R;
-        reinterpret_cast<u32 *>(dst)[threadIdx.x] = reinterpret_cast<const u32 *>(sb)[threadIdx.x];
+        eb[(o * gx + (i64)(blockIdx.x & 7) * (gx >> 3) + (i64)(blockIdx.x >> 3)) * (R / 4) + threadIdx.x] =
+            (unsigned char)((q | q >> 6 | q >> 12 | q >> 18) & 0xffu);
     }
 }
 
-// bytes -> coefficients: c_i * c_o * i^e, e = (3 (Y_i + Y_o) + byte) mod 4.  One lane per inner term, EO outer rows per block,
-// 16-byte non-temporal stores, 1 KiB contiguous per wave instruction.
-constexpr int EO = 4;
-__global__ __launch_bounds__(256) void k_mul_coeff_expand(const unsigned char *__restrict__ eb, i64 gx, int rshift, const int *__restrict__ yi,
+// phase sums -> coefficients: c_i * c_o * i^e, e = (3 (Y_i + Y_o) + s) mod 4, s the pair's 2-bit sum from k_mul_rows_e.  One lane per
+// inner term, one workgroup per 256 consecutive inner terms of ONE outer row: every workgroup writes one contiguous 4 KiB piece with
+// 16-byte non-temporal stores, and dispatch order (by * gx + bx) is address order — the sequential stream of the row kernel (four outer
+// rows per workgroup, four interleaved streams Ni * 16 B apart, ran at 5.4 TB/s).  gx is a multiple of 8, so piece bx is always expanded
+// by XCD bx % 8, whose L2 keeps its eighth of c_i / Y_i across the outer rows (see mul_rows_dev); the surplus workgroups exit.  A byte
+// holds the sums of 4 consecutive inner terms of one row block, which sit in one 256-term piece (R and 256 are multiples of 4).
+// egx = grid.x of the row kernel, rshift = log2 R.
+__global__ __launch_bounds__(256) void k_mul_coeff_expand(const unsigned char *__restrict__ eb, i64 egx, int rshift, const int *__restrict__ yi,
                                                            const int *__restrict__ yo, const double *__restrict__ ci, const double *__restrict__ co,
-                                                           i64 Ni, i64 No, double *__restrict__ out, i64 out_stride) {
+                                                           i64 Ni, double *__restrict__ out, i64 out_stride) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= Ni) return;
-    const i64 R = 1LL << rshift, bx = i >> rshift;
-    const unsigned char *src = eb + ((bx & 7) * (gx >> 3) + (bx >> 3)) * R + (i & (R - 1));
-    const double ar = ci[2 * i], ai = ci[2 * i + 1];
-    const u32 y = (u32)yi[i];
+    const i64 o = blockIdx.y;
+    const i64 R = 1LL << rshift, bx = i >> rshift, r = i & (R - 1);
+    const u32 p = eb[(o * egx + (bx & 7) * (egx >> 3) + (bx >> 3)) * (R >> 2) + (r >> 2)];
+    const double cor = co[2 * o], coi = co[2 * o + 1];                  // wave-uniform: scalar loads
+    const int e = (int)((3u * ((u32)yi[i] + (u32)yo[o]) + (p >> (2 * (r & 3)))) & 3u);
+    double re, im;
+    pair_coefficient(ci[2 * i], ci[2 * i + 1], cor, coi, e, re, im);
     typedef double f64x2 __attribute__((ext_vector_type(2)));
-    f64x2 *dst = reinterpret_cast<f64x2 *>(out) + i;
-    const i64 ob = (i64)blockIdx.y * EO;
-    if (ob + EO <= No) {
-        u32 b[EO];
-#pragma unroll
-        for (int k = 0; k < EO; ++k) b[k] = src[(ob + k) * gx * R];
-#pragma unroll
-        for (int k = 0; k < EO; ++k) {
-            const i64 o = ob + k;
-            const int e = (int)((3u * (y + (u32)yo[o]) + b[k]) & 3u);
-            double re, im;
-            pair_coefficient(ar, ai, co[2 * o], co[2 * o + 1], e, re, im);
-            const f64x2 w = {re, im};
-            __builtin_nontemporal_store(w, dst + o * out_stride);
-        }
-    } else {
-        for (i64 o = ob; o < No; ++o) {
-            const int e = (int)((3u * (y + (u32)yo[o]) + src[o * gx * R]) & 3u);
-            double re, im;
-            pair_coefficient(ar, ai, co[2 * o], co[2 * o + 1], e, re, im);
-            const f64x2 w = {re, im};
-            __builtin_nontemporal_store(w, dst + o * out_stride);
-        }
-    }
+    const f64x2 w = {re, im};
+    __builtin_nontemporal_store(w, reinterpret_cast<f64x2 *>(out) + o * out_stride + i);
 }
 
 // tuning knobs (defaults are the measured best on MI355X; SYMGPU_ROWS_VARIANT="rc,rto,nt[,threads[,pad8]]" overrides for experiments):
@@ -521,11 +511,11 @@ static int mul_rows_coeff_fused(symgpu_op_s *inner, symgpu_op_s *outer, i64 o_be
     int rshift = 0;
     while ((1LL << rshift) < R) ++rshift;
     hipStream_t st = ctx().stream;
-    const i64 max_gy = 65535 / EO * EO;
+    const i64 max_gy = 65535;
     const i64 tile = inner_tile_chunks(n_chunks, Wq);                  // see mul_rows_dev: an inner operand beyond the L2s goes tile by tile
     const i64 gx_max = (((tile < n_chunks ? tile : n_chunks) + 255) / 256 + 7) / 8 * 8;
-    Scratch eb;
-    SG_TRY(eb.alloc((size_t)(No < max_gy ? No : max_gy) * gx_max * R));
+    Scratch eb;                                                         // 2-bit phase sums: R/4 bytes per row block
+    SG_TRY(eb.alloc((size_t)(No < max_gy ? No : max_gy) * gx_max * (R / 4)));
     for (i64 c_lo = 0; c_lo < n_chunks; c_lo += tile) {
         const i64 nc = n_chunks - c_lo < tile ? n_chunks - c_lo : tile;
         const i64 i_lo = c_lo / Wq, ni = nc / Wq;
@@ -552,9 +542,9 @@ static int mul_rows_coeff_fused(symgpu_op_s *inner, symgpu_op_s *outer, i64 o_be
 #undef LAUNCH_E
                 KERNEL_CHECK();
             }
-            dim3 ge((unsigned)((ni + 255) / 256), (unsigned)((ny + EO - 1) / EO));
+            dim3 ge((unsigned)(((ni + 255) / 256 + 7) / 8 * 8), (unsigned)ny);   // one 256-term piece of one outer row per workgroup
             hipLaunchKernelGGL(k_mul_coeff_expand, ge, dim3(256), 0, st, eb.as<unsigned char>(), gx, rshift, yi + i_lo, yo + o_begin + y0, inner->coeff + 2 * i_lo,
-                               outer->coeff + 2 * (o_begin + y0), ni, ny, out->coeff + 2 * (y0 * Ni + i_lo), Ni);
+                               outer->coeff + 2 * (o_begin + y0), ni, out->coeff + 2 * (y0 * Ni + i_lo), Ni);
             KERNEL_CHECK();
         }
     }

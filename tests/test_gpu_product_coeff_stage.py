@@ -1,0 +1,82 @@
+"""GPU: the coefficient stage of the phase-sum product path (product.hip k_mul_rows_e + k_mul_coeff_expand), bit-exact against the C
+oracle.  The row kernel leaves the 2-bit phase sum of every pair, four pairs to a byte; the expansion writes one 256-term piece of one
+outer row per workgroup.  The shapes below end packed bytes and 256-term pieces part-full, cut the inner operand into tiles, need more
+outer rows than one launch's grid.y holds, and write a slab with o_begin > 0 into an output handle that already holds another slab."""
+import numpy as np
+import pytest
+from symmer_amd import kernels, packing, _lib
+from symmer_amd.kernels import DeviceOp
+from oracle import oracle_c as oc
+
+pytestmark = pytest.mark.gpu
+
+# qubits -> 16-byte chunks per row Wq = 1, 2, 4, 8, 16, 32, 64: every row length the phase-sum path serves
+QUBITS = [40, 100, 250, 500, 1000, 2000, 4090]
+
+
+def dyadic(rng, t):
+    return (rng.integers(-8, 9, t) + 1j * rng.integers(-8, 9, t)) / 16.0
+
+
+def gaussian(rng, t):
+    return rng.standard_normal(t) + 1j * rng.standard_normal(t)
+
+
+def check_pairs(rng, n, Ni, No, left):
+    a = packing.pack_rows(rng.random((Ni, 2 * n)) < 0.3); b = packing.pack_rows(rng.random((No, 2 * n)) < 0.3)
+    erows = None
+    for coeffs in (dyadic, gaussian):
+        ca, cb = coeffs(rng, Ni), coeffs(rng, No)
+        rows, coeff = kernels.mul_allpairs(a, ca, b, cb, left)
+        er, ec = oc.mul_allpairs(a, ca, b, cb, left)
+        if erows is None:
+            assert np.array_equal(rows, er)
+            erows = er
+        assert np.array_equal(coeff, ec), (n, Ni, No, left, coeffs.__name__)
+
+
+@pytest.mark.parametrize('left', [True, False])
+@pytest.mark.parametrize('n', QUBITS)
+def test_coeff_stage_ragged_shapes(n, left, monkeypatch):
+    monkeypatch.setenv('SYMGPU_PRODUCT_FUSED', '1')
+    rng = np.random.default_rng(1000 + n + left)
+    for Ni in (1, 3, 5, 255, 257, 1025):
+        for No in (1, 3):
+            check_pairs(rng, n, Ni, No, left)
+
+
+@pytest.mark.parametrize('n', QUBITS)
+def test_coeff_stage_inner_tiles(n, monkeypatch):
+    """SYMGPU_PRODUCT_TILE_MB=0.3: several inner tiles, the last one ragged; every tile is its own pair of launches."""
+    monkeypatch.setenv('SYMGPU_PRODUCT_FUSED', '1')
+    monkeypatch.setenv('SYMGPU_PRODUCT_TILE_MB', '0.3')
+    wq = (n + 63) // 64
+    Ni = 3 * (19661 // wq) + 257
+    check_pairs(np.random.default_rng(1100 + n), n, Ni, 3, n % 2 == 0)
+
+
+def test_coeff_stage_more_outer_rows_than_one_grid():
+    """70,000 outer rows: more than the 65,535 of one launch's grid.y, so the slab goes out in two launches of each kernel."""
+    check_pairs(np.random.default_rng(1200), 20, 3, 70000, True)
+
+
+@pytest.mark.parametrize('n,Ni', [(1000, 257), (40, 1025), (4090, 5)])
+def test_coeff_stage_slab_into_reused_handle(n, Ni):
+    """A slab [o_begin, o_end) with o_begin > 0 written into an output handle that already holds a longer slab of the same product."""
+    rng = np.random.default_rng(1300 + n + Ni)
+    No = 9
+    a = packing.pack_rows(rng.random((Ni, 2 * n)) < 0.3); b = packing.pack_rows(rng.random((No, 2 * n)) < 0.3)
+    ca, cb = gaussian(rng, Ni), gaussian(rng, No)
+    A, B = DeviceOp.upload(a, ca), DeviceOp.upload(b, cb)
+    out = DeviceOp.alloc(No * Ni, (n + 63) // 64, with_coeff=True)
+    lib = _lib.lib()
+    try:
+        for o0, o1 in ((0, No), (4, 7), (8, 9)):
+            _lib.check(lib.symgpu_mul_allpairs_dev(A.handle, B.handle, o0, o1, 1, out.handle))
+            assert out.n_terms == (o1 - o0) * Ni
+            rows, coeff = out.download()
+            er, ec = oc.mul_allpairs(a, ca, b[o0:o1], cb[o0:o1], True)
+            assert np.array_equal(rows, er) and np.array_equal(coeff, ec), (o0, o1)
+    finally:
+        for h in (A, B, out):
+            h.free()
