@@ -14,8 +14,13 @@
  *  - GF(2) matrices: R rows of Wc uint64 words, same bit rule; "leftmost column" = lowest set bit of the
  *    first non-zero word.
  *  - coefficients: complex128 as interleaved double[2] (re, im).
- *  - one context per DEVICE; calls on a device are serialised on its HIP stream; a handle is single-owner and belongs to
- *    the device it was created on.  Multi-GPU = one process per device (symgpu_init + symgpu_comm_*, RCCL over xGMI) or one
+ *  - one context per DEVICE, with a lock: calls on one device are serialised WHOLE (host work, read-backs and kernels of one
+ *    call do not interleave with another thread's call on that device); calls on different devices run concurrently.  Any thread
+ *    may make them.  A handle belongs to the device it was created on and has one owner: several threads may pass the same handle
+ *    to calls that only read it, but freeing or writing a handle while another thread may still pass it is the caller's error.
+ *    Exceptions: the symgpu_comm_* calls take no lock (a collective that never returns must not block the device's other calls);
+ *    symgpu_init* and symgpu_shutdown run before the threads start and after they end, never concurrently with another call.
+ *    Multi-GPU = one process per device (symgpu_init + symgpu_comm_*, RCCL over xGMI) or one
  *    process driving several devices (symgpu_init_all + symgpu_set_device + symgpu_comm_init_all).
  */
 #ifndef SYMGPU_H
@@ -74,7 +79,11 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * 7 / 8: payload bytes copied host -> device / device -> host by this library (operators, coefficients, index arrays, result matrices; not the
  * few-byte counts and flags a call reads back); 9 / 10: operator uploads / downloads (calls that moved a whole operator or its coefficients).
  * The drop-in classes keep their operands on the device between calls; the tests assert through 7-10 that a multi-step workflow
- * (symmer/projection/base.py:44-124, rotate -> project -> cleanup) moves its operator once in and once out. */
+ * (symmer/projection/base.py:44-124, rotate -> project -> cleanup) moves its operator once in and once out.  11: device blocks whose
+ * guard bytes were overwritten (tuning build, SYMGPU_ALLOC_CANARY); 12: the most threads seen using one device's context at once since
+ * load, counted where a call uses the context's state, whichever lock it took (1 while the per-device lock holds); 13: calls that found
+ * their device busy with another thread's call and waited; 14: uses of a device's context by a call that did not hold that context's
+ * lock (0 while the lock is taken on the right device). */
 int symgpu_debug_counter(int which, int64_t *value);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so

@@ -160,7 +160,7 @@ static int cleanup_run(const CleanupRequest &rq, symgpu_op_t *out) {
         }
         if (hback[2]) { r.pl = plan_cleanup(rq, r.sw, true); continue; }   // a long mixed prefix run: redo with a full 64-bit sort over all pairs, same seed
         ok = (hback[1] == 0);
-        if (!ok) { ++r.seed; ++g_hash_reseeds; }      // genuine 64-bit hash collision: reseed and retry
+        if (!ok) { ++r.seed; g_hash_reseeds.fetch_add(1, std::memory_order_relaxed); }   // genuine 64-bit hash collision: reseed and retry
     }
     if (!ok) { set_error("cleanup: 64-bit row-hash collision survived 4 reseeds"); return SYMGPU_E_COLLISION; }
     const PairOperands &p = rq.p;
@@ -261,7 +261,7 @@ static int finish_to_host(symgpu_op_t res, uint64_t *out_rows, double *out_coeff
 
 int symgpu_cleanup(const uint64_t *rows, const double *coeff, int64_t T, int W, double thr, int use_thr, uint64_t *out_rows,
                    double *out_coeff, int64_t capacity, int64_t *n_out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(T >= 0 && W >= 2 && (W % 2) == 0 && capacity >= 0, "cleanup: sizes (W must be 2*Wq)");
     SG_REQUIRE(T == 0 || (rows && coeff), "cleanup: null input");
     symgpu_op_t in = nullptr, res = nullptr;
@@ -275,7 +275,7 @@ int symgpu_cleanup(const uint64_t *rows, const double *coeff, int64_t T, int W, 
 int symgpu_mul_cleanup(const uint64_t *inner, const double *ci, int64_t Ni, const uint64_t *outer, const double *co, int64_t No,
                        int Wq, int inner_is_left, double thr, int use_thr, uint64_t *out_rows, double *out_coeff, int64_t capacity,
                        int64_t *n_out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(Ni >= 0 && No >= 0 && Wq >= 1 && capacity >= 0, "mul_cleanup: sizes");
     if (Ni == 0 || No == 0) { if (n_out) *n_out = 0; return SYMGPU_OK; }
     SG_REQUIRE(inner && outer && ci && co, "mul_cleanup: null input");

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "../../include/symgpu.h"
@@ -51,7 +53,19 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
 
 // ---- context ---------------------------------------------------------------------------------
 struct EmitProbe { const void *key = nullptr; int phase = 0, choice = 0; u64 stamp = 0; float best[2] = {1e30f, 1e30f}; hipEvent_t ev[2] = {nullptr, nullptr}; };
+// The per-device lock of a context (DeviceScope): every call that touches a context holds it for the whole call, so the calls on one device
+// are serialised whole (its host state below — mail words, hash and join tables, epochs, probes — belongs to one call at a time).
+// Recursive, because an entry point may call others.  Copying or assigning a context (symgpu_shutdown resets it with `c = Context()`)
+// leaves the lock and its counter where they are.
+struct ContextLock {
+    std::recursive_mutex mu;
+    std::atomic<int> inside{0};           // threads whose open calls use this context right now (symgpu_debug_counter 12, context.hip ctx())
+    ContextLock() {}
+    ContextLock(const ContextLock &) {}
+    ContextLock &operator=(const ContextLock &) { return *this; }
+};
 struct Context {
+    ContextLock lock;
     bool ready = false;
     int device = -1;
     hipStream_t stream = nullptr;
@@ -103,22 +117,29 @@ void forget_bound_device();                // after a library (RCCL) may have ch
 // first time the enclosing code runs on a device and remembers the answer for that device (the statics belong to the call site)
 #define SG_DEVICE_ONCE(expr)                                                                          \
     ([&]() -> bool {                                                                                  \
-        static u32 _done = 0, _ok = 0;                                                                \
+        static std::atomic<u32> _done{0}, _ok{0};                                                     \
         const u32 _bit = 1u << symgpu::ctx().device;                                                  \
-        if (!(_done & _bit)) { _done |= _bit; if (expr) _ok |= _bit; }                                \
-        return (_ok & _bit) != 0;                                                                     \
+        if (!(_done.fetch_or(_bit) & _bit) && (expr)) _ok.fetch_or(_bit);                             \
+        return (_ok.load() & _bit) != 0;                                                              \
     }())
-extern i64 g_counters[16];                 // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
-                                           // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls)
-inline void count_h2d(size_t bytes) { g_counters[7] += (i64)bytes; }
-inline void count_d2h(size_t bytes) { g_counters[8] += (i64)bytes; }
+extern std::atomic<i64> g_counters[16];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
+                                           // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls),
+                                           // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
+                                           // [14] uses of a context by a call that did not hold its lock
+inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
+inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
+inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }
 int require_ctx();
-// A call that is handed operator handles runs on THEIR device for its duration (and refuses handles of different devices); the
-// thread's own selection comes back when the scope ends.
+// A call that is handed operator handles runs on THEIR device for its duration (and refuses handles of different devices), else on the
+// thread's current device; once that device is settled the scope holds its context's lock until it ends, and the thread's own selection
+// comes back.  Every exported entry point that touches a context enters one (SG_ENTER; tests/test_host_logic.py checks the sources).
+// Lock order: a context lock may be held while the allocator's mutex is taken, never the reverse.
 struct DeviceScope {
     int saved = -1;
     bool active = false;
-    int enter(const struct ::symgpu_op_s *a, const struct ::symgpu_op_s *b = nullptr, const struct ::symgpu_op_s *c = nullptr);
+    int held = -1;                 // the device whose context lock the scope holds
+    u32 using_before = 0;          // the contexts this thread's outer scopes had used
+    int enter(const struct ::symgpu_op_s *a = nullptr, const struct ::symgpu_op_s *b = nullptr, const struct ::symgpu_op_s *c = nullptr);
     ~DeviceScope();
 };
 #define SG_ENTER(...)                   \
@@ -296,7 +317,7 @@ int wide_mul_coeff_dev(const u64 *inner, const double *ci, i64 Ni, const u64 *ou
                        int inner_is_left, double *out_coeff, const PairKeyArgs *keys);
 
 // cleanup_hash.hip, cleanup_driver.hip
-extern i64 g_hash_reseeds;                                      // row-hash collisions that forced a reseed (never seen outside the tests)
+extern std::atomic<i64> g_hash_reseeds;                         // row-hash collisions that forced a reseed (never seen outside the tests)
 int ensure_hash_tables(u64 seed);
 int hash_rows(const u64 *rows, i64 T, int W, u64 *out1);       // h1 of every row (current tables)
 u64 host_row_hash(const u64 *row, int W);                       // the same hash on the host

@@ -234,7 +234,7 @@ using namespace symgpu;
 extern "C" {
 
 int symgpu_ycount(const uint64_t *rows, int64_t T, int Wq, int64_t *out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(T >= 0 && Wq >= 1 && (T == 0 || (rows && out)), "ycount");
     if (T == 0) return SYMGPU_OK;
     Scratch d, o;
@@ -270,7 +270,7 @@ int symgpu_commutes_bits_dev(symgpu_op_t A, int64_t a_begin, int64_t a_end, symg
 }
 
 int symgpu_commutes(const uint64_t *A, int64_t N, const uint64_t *B, int64_t M, int Wq, uint8_t *out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(N >= 0 && M >= 0 && Wq >= 1, "commutes: sizes");
     if (N == 0 || M == 0) return SYMGPU_OK;
     SG_REQUIRE(A && B && out, "commutes: null pointer");

@@ -37,9 +37,21 @@ static Context g_ctxs[SYMGPU_MAX_DEVICES];
 static int g_default_dev = -1;                    // the first device initialised in this process
 static thread_local int t_cur_dev = -1;           // this thread's selection (-1: the default)
 static thread_local int t_bound_dev = -1;         // the device hipSetDevice was last called with on this thread
-i64 g_counters[16] = {0};   // symgpu_debug_counter 1..10 (0 is g_hash_reseeds, cleanup_hash.hip)
+std::atomic<i64> g_counters[16] = {};   // symgpu_debug_counter 1..14 (0 is g_hash_reseeds, cleanup_hash.hip)
 static int cur_index() { return t_cur_dev >= 0 ? t_cur_dev : (g_default_dev >= 0 ? g_default_dev : 0); }
-Context &ctx() { return g_ctxs[cur_index()]; }
+// Use of a context inside a call, recorded where the state is used (ctx()), whatever lock the call's DeviceScope took: a thread that
+// uses a context whose lock it does not hold is counted (symgpu_debug_counter 14), and so are the threads that use one context at the
+// same time (the most of them: counter 12).  Calls that take no lock on purpose (symgpu_comm_*, init, shutdown) open no scope and are
+// not looked at.
+static thread_local int t_scopes = 0;                            // DeviceScopes open on this thread
+static thread_local int t_held[SYMGPU_MAX_DEVICES] = {};         // this thread's holds on each context's lock
+static thread_local u32 t_using = 0;                             // contexts the open scopes of this thread have used (bit per device)
+static void note_use(int d);
+Context &ctx() {
+    const int d = cur_index();
+    if (t_scopes > 0 && !(t_using & (1u << d))) note_use(d);
+    return g_ctxs[d];
+}
 Context *ctx_of_device(int device) { return device >= 0 && device < SYMGPU_MAX_DEVICES ? &g_ctxs[device] : nullptr; }
 void select_device(int device) { t_cur_dev = device; }
 int selected_device() { return t_cur_dev; }
@@ -55,7 +67,7 @@ void note_degraded(const char *what) {
 }
 
 int require_ctx() {
-    Context &c = ctx();
+    Context &c = g_ctxs[cur_index()];          // (not ctx(): DeviceScope::enter calls this before it takes the lock)
     if (!c.ready) {
         set_error("symgpu_init() has not been called for this device (or no HIP device)");
         return SYMGPU_E_NODEVICE;
@@ -73,6 +85,14 @@ void forget_bound_device() { t_bound_dev = -1; }
 
 
 
+static void note_use(int d) {
+    t_using |= 1u << d;
+    if (t_held[d] == 0) bump_counter(14);                       // the call uses a context whose lock it does not hold
+    const i64 users = g_ctxs[d].lock.inside.fetch_add(1) + 1;
+    i64 most = g_counters[12].load(std::memory_order_relaxed);
+    while (users > most && !g_counters[12].compare_exchange_weak(most, users, std::memory_order_relaxed)) {}
+}
+
 int DeviceScope::enter(const symgpu_op_s *a, const symgpu_op_s *b, const symgpu_op_s *c) {
     saved = t_cur_dev;
     active = true;
@@ -85,9 +105,29 @@ int DeviceScope::enter(const symgpu_op_s *a, const symgpu_op_s *b, const symgpu_
         }
         t_cur_dev = first->device;
     }
-    return require_ctx();
+    SG_TRY(require_ctx());
+    const int d = cur_index();                        // the device the call runs on: the handles', else the thread's selection
+    Context &cx = g_ctxs[d];
+    if (!cx.lock.mu.try_lock()) {
+        bump_counter(13);                             // another thread's call is running on this device: wait for it to end
+        cx.lock.mu.lock();
+    }
+    held = d;
+    ++t_held[d];
+    using_before = t_using;
+    ++t_scopes;
+    return SYMGPU_OK;
 }
-DeviceScope::~DeviceScope() { if (active) t_cur_dev = saved; }
+DeviceScope::~DeviceScope() {
+    if (held >= 0) {
+        --t_scopes;
+        for (u32 m = t_using & ~using_before; m; m &= m - 1) g_ctxs[__builtin_ctz(m)].lock.inside.fetch_sub(1);   // this scope's uses end
+        t_using = using_before;
+        --t_held[held];
+        g_ctxs[held].lock.mu.unlock();
+    }
+    if (active) t_cur_dev = saved;
+}
 
 // ---- cached allocator ------------------------------------------------------------------------------------------------------
 // Size classes (power-of-two-ish), freed blocks parked per class until shutdown / release.  A class that has no parked block is
@@ -149,7 +189,7 @@ static void *arena_carve(size_t c, int *chunk) {
         }
         if (pass == 1) break;
         void *base = nullptr;
-        ++g_counters[3];
+        bump_counter(3);
         if (hipMalloc(&base, ARENA_CHUNK) != hipSuccess) { (void)hipGetLastError(); g_arena_on = false; return nullptr; }
         g_chunks.push_back(Chunk{static_cast<char *>(base), ARENA_CHUNK, 0, 0});
     }
@@ -171,7 +211,7 @@ static void canary_check(void *p, size_t bytes) {
     for (size_t k = 0; k < CANARY; ++k)
         if (h[k] != 0xA5) {
             fprintf(stderr, "symgpu CANARY: block of %zu bytes overwritten at +%zu behind its end (value 0x%02x)\n", bytes, k, h[k]);
-            ++g_counters[11];
+            bump_counter(11);
             return;
         }
 }
@@ -232,7 +272,7 @@ int dev_alloc(size_t bytes, void **ptr) {
         }
     }
     std::lock_guard<std::mutex> lk(g_alloc_mu);
-    ++g_counters[3];
+    bump_counter(3);
     g_live[*ptr] = LiveBlock{c, -1, cur_index(), req};
     if (canary_on()) canary_set(*ptr, req);
     return SYMGPU_OK;
@@ -742,19 +782,19 @@ int symgpu_shutdown(void) {
 }
 
 int symgpu_sync(void) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     HIP_TRY(hipStreamSynchronize(ctx().stream));
     return SYMGPU_OK;
 }
 
 int symgpu_device_sync(void) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     HIP_TRY(hipDeviceSynchronize());
     return SYMGPU_OK;
 }
 
 int symgpu_device_name(char *buf, int len) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     if (!buf || len <= 0) return SYMGPU_E_INVALID;
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ctx().device));
@@ -764,7 +804,7 @@ int symgpu_device_name(char *buf, int len) {
 }
 
 int symgpu_mem_info(int64_t *free_bytes, int64_t *total_bytes) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     size_t f = 0, t = 0;
     HIP_TRY(hipMemGetInfo(&f, &t));
     if (free_bytes) *free_bytes = (int64_t)f;
@@ -773,13 +813,13 @@ int symgpu_mem_info(int64_t *free_bytes, int64_t *total_bytes) {
 }
 
 int symgpu_timer_start(void) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     HIP_TRY(hipEventRecord(ctx().ev0, ctx().stream));
     return SYMGPU_OK;
 }
 
 int symgpu_timer_stop(float *ms) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     HIP_TRY(hipEventRecord(ctx().ev1, ctx().stream));
     HIP_TRY(hipEventSynchronize(ctx().ev1));
     float t = 0;
@@ -789,7 +829,7 @@ int symgpu_timer_stop(float *ms) {
 }
 
 int symgpu_membw_probe(int64_t bytes, double *fill_GBps, double *copy_GBps) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(bytes >= (1 << 20), "membw_probe: at least 1 MiB");
     const i64 n = bytes / 16;
     Scratch a, b;
@@ -820,14 +860,15 @@ int symgpu_membw_probe(int64_t bytes, double *fill_GBps, double *copy_GBps) {
 }
 
 int symgpu_prof_enable(int kernel_class, int on) {
+    SG_ENTER();
     SG_REQUIRE(kernel_class >= 0 && kernel_class < SYMGPU_PROF_CLASSES, "prof_enable: class");
     g_prof[kernel_class].on = on != 0;
     return SYMGPU_OK;
 }
 
 int symgpu_debug_counter(int which, int64_t *value) {
-    SG_REQUIRE(value && which >= 0 && which <= 10, "debug_counter: 0 = row-hash reseeds, 1 = rotations done by the one-launch kernel, 2 = its failures (verification / time-out), 3 = device allocations that went to hipMalloc, 4-6 = host nanoseconds of the one-launch rotation (preparation, launch call, wait), 7 / 8 = payload bytes host -> device / device -> host, 9 / 10 = operator uploads / downloads");
-    *value = which == 0 ? g_hash_reseeds : g_counters[which];
+    SG_REQUIRE(value && which >= 0 && which <= 14, "debug_counter: 0 = row-hash reseeds, 1 = rotations done by the one-launch kernel, 2 = its failures (verification / time-out), 3 = device allocations that went to hipMalloc, 4-6 = host nanoseconds of the one-launch rotation (preparation, launch call, wait), 7 / 8 = payload bytes host -> device / device -> host, 9 / 10 = operator uploads / downloads, 11 = canary hits (tuning build), 12 = most threads seen using one device's context at once (1: the calls were serialised), 13 = calls that waited for another thread's call on their device, 14 = uses of a context by a call that did not hold its lock");
+    *value = (which == 0 ? g_hash_reseeds : g_counters[which]).load(std::memory_order_relaxed);
     return SYMGPU_OK;
 }
 
@@ -839,7 +880,7 @@ int symgpu_degraded(char *buf, int len) {
 }
 
 int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(kernel_class >= 0 && kernel_class < SYMGPU_PROF_CLASSES, "prof_read: class");
     HIP_TRY(hipStreamSynchronize(ctx().stream));
     double tot = 0;
@@ -857,13 +898,14 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms) {
 
 // ---- raw device buffers ------------------------------------------------------------------------
 int symgpu_dev_alloc(int64_t bytes, void **ptr) {
+    SG_ENTER();
     SG_REQUIRE(ptr && bytes >= 0, "dev_alloc");
     return dev_alloc((size_t)bytes, ptr);
 }
-int symgpu_dev_free(void *ptr) { return dev_free(ptr); }
+int symgpu_dev_free(void *ptr) { return dev_free(ptr); }   // no context: dev_free files the block under its owning device, under the allocator's mutex
 
 int symgpu_dev_download(const void *dev, void *host, int64_t bytes) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(dev && host && bytes >= 0, "dev_download");
     SG_TRY(download_any(dev, host, (size_t)bytes));
     count_d2h((size_t)bytes);
@@ -871,7 +913,7 @@ int symgpu_dev_download(const void *dev, void *host, int64_t bytes) {
 }
 
 int symgpu_dev_upload(void *dev, const void *host, int64_t bytes) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(dev && host && bytes >= 0, "dev_upload");
     HIP_TRY(hipMemcpyAsync(dev, host, (size_t)bytes, hipMemcpyHostToDevice, ctx().stream));
     HIP_TRY(hipStreamSynchronize(ctx().stream));
@@ -893,7 +935,7 @@ static int reduce_to_host_u64(void (*launch)(const void *, i64, unsigned long lo
 }
 
 int symgpu_dev_checksum_u8(const uint8_t *dev, int64_t n, uint64_t *sum) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(dev && sum && n >= 0, "dev_checksum_u8");
     SG_REQUIRE(((uintptr_t)dev & 15) == 0, "dev_checksum_u8: pointer must be 16-byte aligned");
     return reduce_to_host_u64([](const void *p, i64 n_, unsigned long long *o, hipStream_t s) {
@@ -901,7 +943,7 @@ int symgpu_dev_checksum_u8(const uint8_t *dev, int64_t n, uint64_t *sum) {
 }
 
 int symgpu_dev_popcount_u64(const uint64_t *dev, int64_t n_words, uint64_t *sum) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(dev && sum && n_words >= 0, "dev_popcount_u64");
     return reduce_to_host_u64([](const void *p, i64 n_, unsigned long long *o, hipStream_t s) {
         hipLaunchKernelGGL(k_popc_u64, dim3(2048), dim3(256), 0, s, (const u64 *)p, n_, o); }, dev, n_words, sum);
@@ -909,7 +951,7 @@ int symgpu_dev_popcount_u64(const uint64_t *dev, int64_t n_words, uint64_t *sum)
 
 // ---- operator handles ----------------------------------------------------------------------------
 int symgpu_op_alloc(int64_t capacity_rows, int Wq, int with_coeff, symgpu_op_t *out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(out && capacity_rows >= 0 && Wq >= 1, "op_alloc");
     symgpu_op_s *op = new symgpu_op_s();
     op->device = ctx().device;
@@ -927,16 +969,27 @@ int symgpu_op_alloc(int64_t capacity_rows, int Wq, int with_coeff, symgpu_op_t *
     return SYMGPU_OK;
 }
 
-int symgpu_op_free(symgpu_op_t op) {
-    if (!op) return SYMGPU_OK;
+static void release_op(symgpu_op_t op) {
     op_invalidate(op);
     if (op->rows) dev_free(op->rows);
     if (op->coeff) dev_free(op->coeff);
     delete op;
+}
+
+int symgpu_op_free(symgpu_op_t op) {
+    if (!op) return SYMGPU_OK;
+    const Context *oc = ctx_of_device(op->device);
+    if (oc && oc->ready) {
+        SG_ENTER(op);
+        release_op(op);
+        return SYMGPU_OK;
+    }
+    release_op(op);           // a handle that outlived symgpu_shutdown: dev_free files its blocks under their device without a context
     return SYMGPU_OK;
 }
 
 int symgpu_op_set_rows(symgpu_op_t op, int64_t T) {
+    SG_ENTER(op);
     SG_REQUIRE(op && T >= 0 && T <= op->capacity, "op_set_rows");
     if (T != op->T) op_invalidate(op);
     op->T = T;
@@ -954,7 +1007,7 @@ int symgpu_op_write(symgpu_op_t op, int64_t row_offset, const uint64_t *rows, co
             HIP_TRY(hipMemcpyAsync(op->coeff + 2 * (size_t)row_offset, coeff, (size_t)count * 16, hipMemcpyHostToDevice, ctx().stream));
         HIP_TRY(hipStreamSynchronize(ctx().stream));
         count_h2d((size_t)count * W * 8 + ((coeff && op->coeff) ? (size_t)count * 16 : 0));
-        ++g_counters[9];
+        bump_counter(9);
     }
     op_invalidate(op);
     if (row_offset + count > op->T) op->T = row_offset + count;
@@ -963,12 +1016,14 @@ int symgpu_op_write(symgpu_op_t op, int64_t row_offset, const uint64_t *rows, co
 
 int symgpu_op_copy_rows(symgpu_op_t dst, int64_t dst_offset, symgpu_op_t src, int64_t src_offset, int64_t count) {
     SG_REQUIRE(dst && src && dst != src && dst->Wq == src->Wq, "op_copy_rows: handles");
-    SG_ENTER(dst);                                                     // runs on the destination's device
+    SG_ENTER(dst);                                                     // runs on the destination's device, under its lock only
     SG_REQUIRE(count >= 0 && dst_offset >= 0 && src_offset >= 0 && dst_offset + count <= dst->capacity && src_offset + count <= src->T,
                "op_copy_rows: row range");
     const size_t W = (size_t)2 * dst->Wq;
     if (count > 0 && src->device != dst->device) {
-        // the one call that crosses devices: a peer copy (xGMI) on the destination's stream, after the source's stream has drained
+        // the one call that crosses devices: a peer copy (xGMI) on the destination's stream, after the source's stream has drained.
+        // The source's context is not locked (two copies in opposite directions must not wait for each other): its stream is only
+        // synchronised, and the caller keeps `src` from being written or freed meanwhile, as for any handle it owns
         Context *sc = ctx_of_device(src->device);
         SG_REQUIRE(sc && sc->ready, "op_copy_rows: the source's device has no context");
         HIP_TRY(hipStreamSynchronize(sc->stream));
@@ -986,7 +1041,7 @@ int symgpu_op_copy_rows(symgpu_op_t dst, int64_t dst_offset, symgpu_op_t src, in
 }
 
 int symgpu_op_upload(const uint64_t *rows, const double *coeff, int64_t T, int Wq, symgpu_op_t *out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(out && T >= 0 && Wq >= 1 && (rows || T == 0), "op_upload");
     symgpu_op_t op = nullptr;
     SG_TRY(symgpu_op_alloc(T, Wq, coeff != nullptr, &op));
@@ -997,7 +1052,7 @@ int symgpu_op_upload(const uint64_t *rows, const double *coeff, int64_t T, int W
         if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);   // host buffers are not retained past the call
         if (e != hipSuccess) { symgpu_op_free(op); return hip_fail(e, "op_upload memcpy", __FILE__, __LINE__); }
         count_h2d((size_t)T * 2 * Wq * sizeof(u64) + (coeff ? (size_t)T * 16 : 0));
-        ++g_counters[9];
+        bump_counter(9);
     }
     *out = op;
     return SYMGPU_OK;
@@ -1021,7 +1076,7 @@ int symgpu_op_download(symgpu_op_t op, uint64_t *rows, double *coeff, int64_t ca
             HIP_TRY(hipMemcpyAsync(coeff, op->coeff, (size_t)op->T * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
             count_d2h((size_t)op->T * 16);
         }
-        if (rows || coeff) ++g_counters[10];
+        if (rows || coeff) bump_counter(10);
     }
     HIP_TRY(hipStreamSynchronize(ctx().stream));
     return SYMGPU_OK;
@@ -1052,7 +1107,7 @@ int symgpu_op_set_coeff(symgpu_op_t op, const double *coeff_host) {
         HIP_TRY(hipMemcpyAsync(op->coeff, coeff_host, (size_t)op->T * 16, hipMemcpyHostToDevice, ctx().stream));
         HIP_TRY(hipStreamSynchronize(ctx().stream));              // host buffers are not retained past the call
         count_h2d((size_t)op->T * 16);
-        ++g_counters[9];
+        bump_counter(9);
     }
     return SYMGPU_OK;                                             // the rows did not change: per-handle caches stay
 }
@@ -1085,7 +1140,7 @@ int symgpu_op_ycount(symgpu_op_t op, int64_t *out_host) {
 }
 
 int symgpu_op_upload_bool(const uint8_t *symp, const double *coeff, int64_t T, int n_qubits, symgpu_op_t *out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(out && T >= 0 && n_qubits >= 1 && (symp || T == 0), "op_upload_bool");
     const int Wq = (n_qubits + 63) / 64;
     symgpu_op_t op = nullptr;
@@ -1108,7 +1163,7 @@ int symgpu_op_upload_bool(const uint8_t *symp, const double *coeff, int64_t T, i
         if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);   // host buffers are not retained past the call (and the staging buffer goes)
         if (e != hipSuccess) { symgpu_op_free(op); return hip_fail(e, "op_upload_bool", __FILE__, __LINE__); }
         count_h2d(nb + (coeff ? (size_t)T * 16 : 0));
-        ++g_counters[9];
+        bump_counter(9);
     }
     *out = op;
     return SYMGPU_OK;
@@ -1132,7 +1187,7 @@ int symgpu_op_download_bool(symgpu_op_t op, int n_qubits, uint8_t *symp_out, int
     KERNEL_CHECK();
     SG_TRY(download_any(stage.p, symp_out, nb));
     count_d2h(nb);
-    ++g_counters[10];
+    bump_counter(10);
     return SYMGPU_OK;
 }
 
@@ -1145,7 +1200,7 @@ int symgpu_op_info(symgpu_op_t op, int64_t *T, int *Wq, int64_t *capacity_rows) 
 }
 
 int symgpu_op_random(int64_t T, int n_qubits, double density, uint64_t seed, symgpu_op_t *out) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(out && T >= 0 && n_qubits >= 1 && density >= 0.0 && density <= 1.0, "op_random");
     int Wq = (n_qubits + 63) / 64;
     symgpu_op_t op = nullptr;

@@ -962,13 +962,13 @@ using namespace symgpu;
 extern "C" {
 
 int symgpu_rref_dev(uint64_t *rows_dev, int64_t R, int64_t Wc, int64_t *xor_count, int64_t *pivots_host) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(R >= 0 && Wc >= 0 && (rows_dev || R * Wc == 0), "rref_dev");
     return rref_dev(rows_dev, R, Wc, xor_count, pivots_host);
 }
 
 int symgpu_rref(uint64_t *rows, int64_t R, int64_t Wc, int64_t *xor_count, int64_t *pivots) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(R >= 0 && Wc >= 0 && (rows || R * Wc == 0), "rref");
     if (xor_count) *xor_count = 0;
     if (R == 0 || Wc == 0) {
@@ -1029,7 +1029,7 @@ int symgpu_symmetry_kernel_dev(symgpu_op_t H, int n_qubits, uint64_t *out, int64
 
 int symgpu_symmetry_kernel(const uint64_t *H, int64_t M, int n_qubits, int Wq, uint64_t *out, int64_t capacity, int64_t *k,
                            int64_t *xor_count) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(M >= 0 && n_qubits >= 1 && Wq == (n_qubits + 63) / 64 && k, "symmetry_kernel: sizes");
     SG_REQUIRE(H || M == 0, "symmetry_kernel: null input");
     symgpu_op_t op = nullptr;

@@ -625,7 +625,7 @@ int symgpu_mul_allpairs_dev(symgpu_op_t inner, symgpu_op_t outer, int64_t o_begi
 
 int symgpu_mul_allpairs(const uint64_t *inner, const double *ci, int64_t Ni, const uint64_t *outer, const double *co,
                         int64_t No, int Wq, int inner_is_left, uint64_t *out_rows, double *out_coeff) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(Ni >= 0 && No >= 0 && Wq >= 1, "mul_allpairs: sizes");
     if (Ni == 0 || No == 0) return SYMGPU_OK;
     SG_REQUIRE(inner && outer && ci && co && out_rows && out_coeff, "mul_allpairs: null pointer");

@@ -138,6 +138,7 @@ extern "C" {
 
 int symgpu_rotate_single_dev_n(symgpu_op_t in, const uint64_t *q_row_host, double cos_t, double sin_t, int clifford_k, double thr,
                                symgpu_op_t *out, int *all_commute, int64_t *n_out) {
+    SG_ENTER(in);
     SG_REQUIRE(n_out, "rotate_single_dev_n: null argument");
     *n_out = 0;
     SG_TRY(symgpu_rotate_single_dev(in, q_row_host, cos_t, sin_t, clifford_k, thr, out, all_commute));
@@ -262,7 +263,7 @@ int symgpu_perform_rotations_dev(symgpu_op_t in, const uint64_t *q_rows_host, co
 }
 
 int symgpu_debug_rotation_trace(uint64_t *out, int max_workgroups, int *n_workgroups) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(out && n_workgroups && max_workgroups >= 0, "debug_rotation_trace");
     return rotate_resident_trace(out, max_workgroups, n_workgroups);
 }
@@ -270,7 +271,7 @@ int symgpu_debug_rotation_trace(uint64_t *out, int max_workgroups, int *n_workgr
 int symgpu_rotate_single(const uint64_t *rows, const double *coeff, int64_t N, int Wq, const uint64_t *q_row, double cos_t, double sin_t,
                          int clifford_k, double thr, uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out,
                          int *all_commute) {
-    SG_TRY(require_ctx());
+    SG_ENTER();
     SG_REQUIRE(N >= 0 && Wq >= 1 && q_row && all_commute && n_out, "rotate_single: arguments");
     SG_REQUIRE(N == 0 || (rows && coeff), "rotate_single: null input");
     symgpu_op_t in = nullptr, res = nullptr;

@@ -799,7 +799,7 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
     }
     hipError_t e = hipGetLastError();
     const i64 t_wait = host_ns();
-    g_counters[4] += t_launch - t_enter; g_counters[5] += t_wait - t_launch;
+    bump_counter(4, t_launch - t_enter); bump_counter(5, t_wait - t_launch);
     if (e != hipSuccess) { symgpu_op_free(res); c.res_dirty = true; return hip_fail(e, "rotate resident", __FILE__, __LINE__); }
     // One workgroup reports the counts as soon as they are final (after the second all-gather, while the rows are still being written):
     // poll the two tagged words in pinned memory instead of synchronising the stream — whatever the caller enqueues next is stream
@@ -829,13 +829,13 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
         if (e != hipSuccess) { symgpu_op_free(res); c.res_dirty = true; return hip_fail(e, "rotate resident", __FILE__, __LINE__); }
         if (!seen) { w0 = 0; w1 = 1ULL << 44; }                                   // no report at all: code 1
     }
-    g_counters[6] += host_ns() - t_wait;
+    bump_counter(6, host_ns() - t_wait);
     RotCounts hc;
     hc.nC = (u32)(w0 >> 22) & 0x3FFFFFu; hc.nA = (u32)w0 & 0x3FFFFFu; hc.nN = (u32)(w1 >> 22) & 0x3FFFFFu; hc.nAnti = (u32)w1 & 0x3FFFFFu;
     hc.dup = (u32)(w1 >> 44) & 0xFu;
     if (hc.dup != 0) {                                                             // verification failed (2), timed out (3), or no report at all (1)
         symgpu_op_free(res);
-        ++g_counters[2];
+        bump_counter(2);
         if (hc.dup != 2) {                                                         // time-out: arrival counts are in an unknown state
             c.res_disabled = true; c.res_epoch = 0;
             note_degraded("one-launch rotation (k_rot_resident) off: an in-kernel wait timed out (workgroups not co-resident?); rotations take the multi-launch kernels");
@@ -846,7 +846,7 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
         return SYMGPU_OK;
     }
     *done = 1;
-    ++g_counters[1];
+    bump_counter(1);
     if (hc.nAnti == 0) { symgpu_op_free(res); *all_commute = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133)
     res->T = (i64)hc.nC + hc.nA + hc.nN;
     res->dup_free = clifford ? in->dup_free : 1;

@@ -484,14 +484,12 @@ int symgpu_to_csr_count(symgpu_op_t op, int n_qubits, int64_t *nnz, int64_t *fil
 
 int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *indptr, int index_bytes) {
     SG_REQUIRE(plan, "to_csr_fill: null plan");
+    // the plan goes whatever happens, after the scope below has ended (dev_free files a block under its owning device: no context needed)
+    struct PlanRelease { symgpu_csr_t p; ~PlanRelease() { csr_release(p); } } release{plan};
     symgpu_op_s scope_op;                         // the plan's device, entered the way a call with a handle enters it
     scope_op.device = plan->device;
-    DeviceScope scope;
-    int rc = scope.enter(&scope_op);
-    if (rc != SYMGPU_OK) {
-        csr_release(plan);                        // dev_free files a block under its owning device: no context needed
-        return rc;
-    }
+    SG_ENTER(&scope_op);
+    int rc = SYMGPU_OK;
     if (data || indices || indptr) {
         if (!(indptr && (index_bytes == 4 || index_bytes == 8) && (plan->nnz == 0 || (data && indices)))) {
             set_error("invalid argument: to_csr_fill: buffers / index_bytes");
@@ -504,7 +502,6 @@ int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *ind
         const hipError_t e = hipStreamSynchronize(ctx().stream);
         if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
     }
-    csr_release(plan);
     return rc;
 }
 

@@ -348,3 +348,135 @@ def test_rotation_args_clifford_detection(angle):
         assert (k in (2, 3)) == (int_part in (2, 3))        # negates
     else:
         assert k == -1 and cos_t == np.cos(angle) and sin_t == np.sin(angle)
+
+
+# ---- every exported entry point that touches a device context holds that context's lock (SG_ENTER, common.h) ------------------------
+# The calls that deliberately take no lock, each with its reason.  Every name here must still be defined (the list cannot rot).
+UNLOCKED_ENTRY_POINTS = {
+    'symgpu_comm_available': 'loads librccl only; touches no context',
+    'symgpu_comm_unique_id': 'RCCL bring-up: no lock may be held inside RCCL (a watchdog may give up on it)',
+    'symgpu_comm_init': 'RCCL bring-up on a watchdog thread that may never return; the device must stay usable meanwhile',
+    'symgpu_comm_init_all': 'RCCL bring-up: no lock may be held inside RCCL',
+    'symgpu_comm_abandon': 'disowns a bring-up a watchdog gave up on; must not wait for anything',
+    'symgpu_comm_destroy': 'RCCL teardown: no lock may be held inside RCCL',
+    'symgpu_comm_allgather_op': 'RCCL collective: the first one runs on a watchdog thread while the main thread goes on',
+    'symgpu_comm_allgather_ops': 'RCCL collective over all devices: no lock may be held inside RCCL',
+    'symgpu_comm_barrier': 'RCCL collective: no lock may be held inside RCCL',
+    'symgpu_init': 'creates a context; documented as before the threads start',
+    'symgpu_init_all': 'creates the contexts; documented as before the threads start',
+    'symgpu_shutdown': 'destroys the contexts; documented as after the threads end',
+    'symgpu_set_device': "sets the calling thread's selection only (plus init of a new context)",
+    'symgpu_current_device': "reads the calling thread's selection",
+    'symgpu_device_count': 'asks the runtime; touches no context',
+    'symgpu_n_initialised': 'counts ready contexts; touches none of their state',
+    'symgpu_degraded': 'has its own mutex',
+    'symgpu_debug_counter': 'reads atomic counters',
+    'symgpu_op_info': "reads the handle's own fields (a handle has one owner)",
+    'symgpu_dev_free': "allocator only: files the block under its owning device, under the allocator's mutex; needs no context",
+}
+
+
+def _strip_c_comments_and_strings(src):
+    """`src` with comments, string and character literals blanked (same length), so that braces in them do not count."""
+    out, i, n = [], 0, len(src)
+    while i < n:
+        c = src[i]
+        if src.startswith('//', i):
+            j = src.find('\n', i)
+            j = n if j < 0 else j
+            out.append(' ' * (j - i)); i = j
+        elif src.startswith('/*', i):
+            j = src.find('*/', i + 2)
+            j = n if j < 0 else j + 2
+            out.append(re.sub(r'[^\n]', ' ', src[i:j])); i = j
+        elif c in '"\'':
+            j = i + 1
+            while j < n and src[j] != c:
+                j += 2 if src[j] == '\\' else 1
+            out.append(c + ' ' * (j - i - 1) + c); i = j + 1
+        else:
+            out.append(c); i += 1
+    return ''.join(out)
+
+
+def _entry_point_bodies(src):
+    """{name: body} of every `int symgpu_*(...) {...}` definition in one translation unit (declarations are skipped)."""
+    clean = _strip_c_comments_and_strings(src)
+    bodies = {}
+    for m in re.finditer(r'^int\s+(symgpu_\w+)\s*\(', clean, re.M):
+        depth, i = 0, m.end() - 1
+        while True:                                    # the parameter list
+            depth += {'(': 1, ')': -1}.get(clean[i], 0)
+            if depth == 0:
+                break
+            i += 1
+        j = i + 1
+        while clean[j].isspace():
+            j += 1
+        if clean[j] != '{':
+            continue
+        depth, k = 0, j
+        while True:
+            depth += {'{': 1, '}': -1}.get(clean[k], 0)
+            if depth == 0:
+                break
+            k += 1
+        assert m.group(1) not in bodies, f'{m.group(1)} defined twice'
+        bodies[m.group(1)] = clean[j:k + 1]
+    return bodies
+
+
+def _lock_violations(sources, allow):
+    """Problems with the lock discipline of `sources` ({file name: text}) under the allowlist `allow`."""
+    bodies = {}
+    for fname, src in sources.items():
+        for name, body in _entry_point_bodies(src).items():
+            assert name not in bodies, f'{name} defined in two files'
+            bodies[name] = (fname, body)
+    problems = [f'{name} ({fname}) takes no context lock: begin it with SG_ENTER(...) or list it in UNLOCKED_ENTRY_POINTS with a reason'
+                for name, (fname, body) in sorted(bodies.items()) if name not in allow and 'SG_ENTER(' not in body]
+    problems += [f'{name} is in UNLOCKED_ENTRY_POINTS but no longer defined' for name in sorted(allow) if name not in bodies]
+    problems += [f'{name} is in UNLOCKED_ENTRY_POINTS but takes the lock all the same' for name in sorted(allow)
+                 if name in bodies and 'SG_ENTER(' in bodies[name][1]]
+    return problems, bodies
+
+
+def _hip_sources():
+    csrc = os.path.join(ROOT, 'symmer_amd', 'csrc')
+    return {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith('.hip')}
+
+
+def test_every_entry_point_takes_its_context_lock():
+    problems, bodies = _lock_violations(_hip_sources(), UNLOCKED_ENTRY_POINTS)
+    assert not problems, '\n'.join(problems)
+    assert len(bodies) >= 80, f'the scan found only {len(bodies)} entry points: has the definition style changed?'
+    assert all(reason.strip() for reason in UNLOCKED_ENTRY_POINTS.values())
+    # every entry point the header declares is defined where the scan looks (an `int` definition), except the one that returns text
+    header = open(os.path.join(ROOT, 'include', 'symgpu.h')).read()
+    declared = set(re.findall(r'^int\s+(symgpu_\w+)\s*\(', _strip_c_comments_and_strings(header), re.M))
+    assert declared <= set(bodies), f'declared but not found by the scan: {sorted(declared - set(bodies))}'
+
+
+def test_lock_scan_names_an_entry_point_that_drops_its_lock_and_a_stale_allowlist():
+    sources = _hip_sources()
+    # SG_ENTER removed from one entry point: the scan names it
+    fname = 'context.hip'
+    body = _entry_point_bodies(sources[fname])['symgpu_op_scale']
+    assert body.count('SG_ENTER(op);') == 1
+    start = sources[fname].index('int symgpu_op_scale(')
+    broken = dict(sources)
+    broken[fname] = sources[fname][:start] + sources[fname][start:].replace('SG_ENTER(op);', 'SG_TRY(require_ctx());', 1)
+    problems, _ = _lock_violations(broken, UNLOCKED_ENTRY_POINTS)
+    assert len(problems) == 1 and problems[0].startswith('symgpu_op_scale (context.hip) takes no context lock'), problems
+    # a name taken off the allowlist: the scan names it
+    allow = dict(UNLOCKED_ENTRY_POINTS)
+    del allow['symgpu_comm_barrier']
+    problems, _ = _lock_violations(sources, allow)
+    assert len(problems) == 1 and problems[0].startswith('symgpu_comm_barrier (comm.hip) takes no context lock'), problems
+    # a name on the allowlist that no longer exists: the scan names it
+    problems, _ = _lock_violations(sources, dict(UNLOCKED_ENTRY_POINTS, symgpu_gone='removed'))
+    assert problems == ['symgpu_gone is in UNLOCKED_ENTRY_POINTS but no longer defined'], problems
+    # braces and SG_ENTER inside comments and strings do not count
+    fake = {'x.hip': 'int symgpu_fake(int a) {\n    // SG_ENTER(a); }\n    const char *s = "SG_ENTER( {";\n    return 0;\n}\n'}
+    problems, bodies = _lock_violations(fake, {})
+    assert list(bodies) == ['symgpu_fake'] and len(problems) == 1, problems
