@@ -35,7 +35,8 @@ extern "C" {
 #define SYMGPU_E_INVALID (-1)   /* bad argument (null pointer, negative size, Wq mismatch, T >= 2^32 for cleanup ...) */
 #define SYMGPU_E_HIP (-2)       /* a HIP runtime call failed; see symgpu_last_error() */
 #define SYMGPU_E_NOMEM (-3)     /* device allocation failed */
-#define SYMGPU_E_CAPACITY (-4)  /* caller-supplied output capacity too small; *n_out holds the required row count */
+#define SYMGPU_E_CAPACITY (-4)  /* caller-supplied output capacity too small; *n_out (*k) holds the required row count and the output
+                                 * buffers are untouched: call with capacity 0 to ask, allocate, call again */
 #define SYMGPU_E_NODEVICE (-5)  /* no HIP device / symgpu_init not called */
 #define SYMGPU_E_COLLISION (-6) /* row-hash collision survived every reseed (never observed; exactness guard) */
 #define SYMGPU_E_RCCL (-7)      /* RCCL could not be loaded or a collective failed */
@@ -123,7 +124,9 @@ int symgpu_op_scale(symgpu_op_t op, double re, double im, int conjugate_first);
 int symgpu_op_ycount(symgpu_op_t op, int64_t *out_host);
 int symgpu_op_upload_bool(const uint8_t *symp /* [T][2n] */, const double *coeff /* may be NULL */, int64_t T, int n_qubits, symgpu_op_t *out);
 int symgpu_op_download_bool(symgpu_op_t op, int n_qubits, uint8_t *symp_out /* [capacity_rows][2n] */, int64_t capacity_rows);
-/* XOR-fold of all packed rows (2*Wq words) and plain sum of coefficients: size-independent checksums */
+/* XOR-fold of all packed rows (2*Wq words) and plain sum of coefficients: size-independent checksums.  Either output may be NULL; an
+ * operator without coefficients (or without rows) gives a zero sum.  The fold is defined for rows of up to 8,192 words (Wq <= 4,096: one
+ * word per column in 64 KiB of LDS); wider rows are refused with SYMGPU_E_INVALID when xor_words is asked for. */
 int symgpu_op_checksum(symgpu_op_t op, uint64_t *xor_words /* [2*Wq] */, double *coeff_sum /* [2] */);
 /* number of set bits in all packed rows: sum_{i,o} |a_i ^ b_o| of a product slab follows from the operands' bit-column counts in O(N + M) */
 int symgpu_op_popcount(symgpu_op_t op, uint64_t *sum);
@@ -142,7 +145,9 @@ int symgpu_dev_alloc(int64_t bytes, void **ptr);
 int symgpu_dev_free(void *ptr);
 int symgpu_dev_download(const void *dev, void *host, int64_t bytes);
 int symgpu_dev_upload(void *dev, const void *host, int64_t bytes);
-int symgpu_dev_checksum_u8(const uint8_t *dev, int64_t n, uint64_t *sum); /* sum of bytes (number of commuting pairs) */
+/* number of 1 bytes among n bytes that must each be 0 or 1 (a commutation table: the number of commuting pairs); dev 16-byte aligned.
+ * Other byte values are not summed: whole 16-byte groups are counted by their set bits. */
+int symgpu_dev_checksum_u8(const uint8_t *dev, int64_t n, uint64_t *sum);
 int symgpu_dev_popcount_u64(const uint64_t *dev, int64_t n_words, uint64_t *sum);
 
 /* ---- a3/a4: all-pairs product  (base.py:764-794 `_multiply_by_operator`, :821-859 `__mul__`) ----
@@ -158,7 +163,8 @@ int symgpu_mul_allpairs_dev(symgpu_op_t inner, symgpu_op_t outer, int64_t o_begi
 
 /* ---- a5: symplectic_cleanup / PauliwordOp.cleanup (utils.py:230-279, base.py:617-638) ------------
  * Merge duplicate rows (sequential sum in input order), keep |c| > thr (strict) if use_thr, output in
- * first-occurrence order.  W = words per row (2*Wq).  n_out always receives the row count. */
+ * first-occurrence order.  W = words per row (2*Wq).  n_out always receives the row count, also with SYMGPU_E_CAPACITY (the output
+ * buffers are then untouched; they may be NULL when capacity is 0). */
 int symgpu_cleanup(const uint64_t *rows, const double *coeff, int64_t T, int W, double thr, int use_thr,
                    uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out);
 int symgpu_cleanup_dev(symgpu_op_t in, double thr, int use_thr, symgpu_op_t *out);
@@ -191,7 +197,9 @@ int symgpu_merge_indexed_dev(const symgpu_op_t *parts, int n_parts, int key_bits
  * clifford_k < 0: non-Clifford: cleanup([commuting, cos*anticommuting, -i*sin*(anticommuting*Q)], thr)
  * clifford_k >= 0 (= round(2*angle/pi)): [rotated anticommuting rows, commuting rows], no merge;
  *   odd k: c*i^e*(-i); k in {2,3}: negated (not reduced mod 4, base.py:1148).
- * *all_commute = 1 (and out untouched / *out = NULL) when every row commutes with Q. */
+ * *all_commute = 1 (and out untouched / *out = NULL) when every row commutes with Q — also when there is no row (N = 0); the host-array
+ * call then sets *n_out = N: the result is the input, which the caller still holds.  Otherwise *n_out is the result's row count, also
+ * when the call returns SYMGPU_E_CAPACITY (out untouched). */
 int symgpu_rotate_single(const uint64_t *rows, const double *coeff, int64_t N, int Wq, const uint64_t *q_row,
                          double cos_t, double sin_t, int clifford_k, double thr,
                          uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out, int *all_commute);

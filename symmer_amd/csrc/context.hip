@@ -344,6 +344,7 @@ ProfScope::~ProfScope() {
 }
 
 // ---- small kernels -----------------------------------------------------------------------------
+constexpr size_t XOR_FOLD_MAX_LDS = 64 << 10;     // dynamic LDS of k_xor_fold: W * 8 bytes
 __global__ void k_xor_fold(const u64 *__restrict__ rows, i64 T, int W, u64 *__restrict__ out) {
     // out[w] ^= XOR over rows; one block per grid-stride chunk, lanes over (row, word) pairs
     extern __shared__ u64 s_fold[];
@@ -430,7 +431,9 @@ __global__ void k_random_op(u64 *__restrict__ rows, double *__restrict__ coeff, 
     }
 }
 
-// coefficients in place: c <- (conjugate_first ? conj(c) : c) * (re + i im), plain IEEE products (no contraction: NumPy's complex multiply)
+// coefficients in place: c <- (conjugate_first ? conj(c) : c) * (re + i im), plain IEEE products: every partial product and the sum are
+// rounded once, no contraction.  That is NumPy's complex128 SCALAR multiply bit for bit; NumPy's ARRAY multiply contracts with FMA in its
+// SIMD loop on x86-64 and differs by an ulp on about two general products in five ("Product coefficients").
 __global__ __launch_bounds__(256) void k_scale_coeff(double *__restrict__ c, i64 T, double re, double im, int conjugate_first) {
     const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;
@@ -1227,6 +1230,8 @@ int symgpu_op_checksum(symgpu_op_t op, uint64_t *xor_words, double *coeff_sum) {
     SG_ENTER(op);
     SG_REQUIRE(op, "op_checksum: null handle");
     int W = 2 * op->Wq;
+    // k_xor_fold keeps one word per column in dynamic LDS: 64 KiB is what a workgroup gets without an attribute
+    SG_REQUIRE(!xor_words || (size_t)W * sizeof(u64) <= XOR_FOLD_MAX_LDS, "op_checksum: rows of more than 8,192 words (Wq > 4,096) cannot be folded");
     Scratch acc;
     SG_TRY(acc.alloc((size_t)W * sizeof(u64) + 2 * sizeof(double)));
     HIP_TRY(hipMemsetAsync(acc.p, 0, (size_t)W * sizeof(u64) + 2 * sizeof(double), ctx().stream));
