@@ -108,7 +108,10 @@ struct Context {
     bool res_disabled = false;     // a barrier timed out once (workgroups not co-resident): the process keeps to the multi-launch paths
     u32 res_finished_base = 0, res_host_tag = 0;   // one-launch rotation: arrival counter base of the next launch, tag of its report
 };
-Context &ctx();                            // the calling thread's current device's context
+// internal names shared by context.hip, alloc.hip, transfer.hip and op_handles.hip only: kept out of the library's dynamic symbols
+#define SG_HIDDEN __attribute__((visibility("hidden")))
+Context &ctx();                            // the calling thread's current device's context (inside a DeviceScope: counted as a use of it)
+SG_HIDDEN int cur_index();                 // that device's index and nothing else: no use is counted (the allocator, require_ctx)
 Context *ctx_of_device(int device);
 void select_device(int device);            // this thread's current device (no HIP call; require_ctx binds the runtime)
 int selected_device();
@@ -157,11 +160,14 @@ struct ProfScope {
     ~ProfScope();
 };
 
-// cached device allocator (hipMalloc is slow; rotations chain many small temporaries)
-int dev_alloc(size_t bytes, void **ptr);
+// alloc.hip — cached device allocator (hipMalloc is slow; rotations chain many small temporaries)
+SG_HIDDEN void dev_alloc_init(int device);                        // once per device, from its init
+int dev_alloc(size_t bytes, void **ptr);                          // on the CURRENT device
+int dev_free(void *ptr);                                          // back to the OWNING device's lists
+void dev_cache_release();                                         // the CURRENT device's parked blocks and idle arena chunks
+// transfer.hip
 void prefault_host(void *dst, size_t bytes);                      // touch the pages of a large D2H destination first
-int dev_free(void *ptr);
-void dev_cache_release();
+SG_HIDDEN int download_any(const void *dev, void *host, size_t bytes);   // device -> pageable host memory, any size; returns with the data there
 
 // RAII scratch buffer on the cached allocator
 struct Scratch {
@@ -216,7 +222,7 @@ int op_wordmajor(symgpu_op_s *op, i64 mult, const u64 **out, i64 *pad);
 int op_ycount(symgpu_op_s *op, const int **out);
 void op_invalidate(symgpu_op_s *op);
 
-// the n_a + n_b <= 8 device words a[0..n_a) ++ b[0..n_b) to the host, behind everything queued on the stream so far (context.hip)
+// the n_a + n_b <= 8 device words a[0..n_a) ++ b[0..n_b) to the host, behind everything queued on the stream so far (transfer.hip)
 int read_back_words(const u32 *a, int n_a, const u32 *b, int n_b, u32 *host_out, const u32 *c1 = nullptr);
 struct ReadBack { int n; u32 seq; u32 plain[8]; };
 int read_back_post(const u32 *a, int n_a, const u32 *b, int n_b, ReadBack *rb, const u32 *c1 = nullptr /* one more word */);   // ... more work may be queued before the wait

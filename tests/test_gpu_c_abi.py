@@ -565,6 +565,15 @@ def refusal_cases():
     keepalive = (buf, idx_bad, idx_neg, keep_bad, keep_ok, parts)
     cases = [
         # context.hip
+        ('debug_counter/which', 'debug_counter', lambda L, o: L.symgpu_debug_counter(15, byref(n64))),
+        ('current_device/null', 'current_device', lambda L, o: L.symgpu_current_device(None)),
+        ('n_initialised/null', 'n_initialised', lambda L, o: L.symgpu_n_initialised(None)),
+        # alloc.hip
+        ('dev_alloc/negative', 'dev_alloc', lambda L, o: L.symgpu_dev_alloc(I64(-1), byref(out))),
+        # transfer.hip
+        ('dev_upload/null-host', 'dev_upload', lambda L, o: L.symgpu_dev_upload(o.dev, None, I64(16))),
+        ('dev_download/negative', 'dev_download', lambda L, o: L.symgpu_dev_download(o.dev, B, I64(-1))),
+        # op_handles.hip
         ('op_copy_rows/same-handle', 'op_copy_rows', lambda L, o: L.symgpu_op_copy_rows(o.a, I64(0), o.a, I64(0), I64(1))),
         ('op_copy_rows/Wq-mismatch', 'op_copy_rows', lambda L, o: L.symgpu_op_copy_rows(o.a, I64(0), o.w1, I64(0), I64(1))),
         ('op_copy_rows/null-dst', 'op_copy_rows', lambda L, o: L.symgpu_op_copy_rows(None, I64(0), o.a, I64(0), I64(1))),
@@ -593,24 +602,20 @@ def refusal_cases():
         ('op_set_coeff/null', 'op_set_coeff', lambda L, o: L.symgpu_op_set_coeff(o.a, None)),
         ('op_scale/no-coefficients', 'op_scale', lambda L, o: L.symgpu_op_scale(o.b, DBL(2.0), DBL(0.0), 0)),
         ('op_ycount/null-out', 'op_ycount', lambda L, o: L.symgpu_op_ycount(o.a, None)),
-        ('op_popcount/null-sum', 'op_popcount', lambda L, o: L.symgpu_op_popcount(o.a, None)),
-        ('op_checksum/null-handle', 'op_checksum', lambda L, o: L.symgpu_op_checksum(None, B, B)),
-        ('op_checksum/too-wide', 'op_checksum', lambda L, o: L.symgpu_op_checksum(o.wide, B, None)),
         ('op_random/density', 'op_random', lambda L, o: L.symgpu_op_random(I64(4), 10, DBL(1.5), U64(1), byref(out))),
         ('op_random/negative-density', 'op_random', lambda L, o: L.symgpu_op_random(I64(4), 10, DBL(-0.1), U64(1), byref(out))),
         ('op_random/n-0', 'op_random', lambda L, o: L.symgpu_op_random(I64(4), 0, DBL(0.5), U64(1), byref(out))),
-        ('dev_alloc/negative', 'dev_alloc', lambda L, o: L.symgpu_dev_alloc(I64(-1), byref(out))),
-        ('dev_upload/null-host', 'dev_upload', lambda L, o: L.symgpu_dev_upload(o.dev, None, I64(16))),
-        ('dev_download/negative', 'dev_download', lambda L, o: L.symgpu_dev_download(o.dev, B, I64(-1))),
+        # checksum.hip
+        ('op_popcount/null-sum', 'op_popcount', lambda L, o: L.symgpu_op_popcount(o.a, None)),
+        ('op_checksum/null-handle', 'op_checksum', lambda L, o: L.symgpu_op_checksum(None, B, B)),
+        ('op_checksum/too-wide', 'op_checksum', lambda L, o: L.symgpu_op_checksum(o.wide, B, None)),
         # the pointer is inside a live block and is never dereferenced: the alignment is a host-side comparison
         ('dev_checksum_u8/alignment', 'dev_checksum_u8', lambda L, o: L.symgpu_dev_checksum_u8(P(o.dev.value + 1), I64(16), byref(n64))),
         ('dev_checksum_u8/negative-n', 'dev_checksum_u8', lambda L, o: L.symgpu_dev_checksum_u8(o.dev, I64(-1), byref(n64))),
         ('dev_checksum_u8/null-sum', 'dev_checksum_u8', lambda L, o: L.symgpu_dev_checksum_u8(o.dev, I64(16), None)),
         ('dev_popcount_u64/null-sum', 'dev_popcount_u64', lambda L, o: L.symgpu_dev_popcount_u64(o.dev, I64(2), None)),
-        ('debug_counter/which', 'debug_counter', lambda L, o: L.symgpu_debug_counter(15, byref(n64))),
+        # rotate_driver.hip
         ('debug_rotation_trace/null-out', 'debug_rotation_trace', lambda L, o: L.symgpu_debug_rotation_trace(None, 0, byref(i32))),
-        ('current_device/null', 'current_device', lambda L, o: L.symgpu_current_device(None)),
-        ('n_initialised/null', 'n_initialised', lambda L, o: L.symgpu_n_initialised(None)),
         # cleanup_driver.hip
         ('cleanup/W-odd', 'cleanup', lambda L, o: L.symgpu_cleanup(R(o), C(o), I64(12), 3, DBL(0.0), 0, B, B, I64(12), byref(n64))),
         ('cleanup/W-0', 'cleanup', lambda L, o: L.symgpu_cleanup(R(o), C(o), I64(12), 0, DBL(0.0), 0, B, B, I64(12), byref(n64))),

@@ -494,7 +494,7 @@ def test_cfg5_adjacency_slice_full_width():
 
 def test_large_result_arrives_whole_through_the_api():
     """A commutation table of more than 2 GiB comes to the host in 1 GiB pieces whose pages are touched while the previous piece travels
-    (context.hip download_pipelined): `P.commutes_termwise(P)` of 52,000 terms (2.7 GB) through the drop-in class
+    (transfer.hip download_pipelined): `P.commutes_termwise(P)` of 52,000 terms (2.7 GB) through the drop-in class
     equals the same table fetched band by band in copies below the gate, and random blocks equal the oracle's."""
     from symmer_amd import PauliwordOp
     lib = _lib.lib()

@@ -471,7 +471,7 @@ def test_squared_operator_path_equals_general_pair_path(n, N, monkeypatch):
 
 def test_read_backs_through_mapped_memory_equal_plain_copies(monkeypatch):
     """Counts and status words that a call needs on the host in the middle of its work travel through mapped host memory (a one-wavefront
-    kernel + a polled sequence number, context.hip); SYMGPU_READBACK_PLAIN=1 makes every one of them a copy + stream synchronisation.
+    kernel + a polled sequence number, transfer.hip); SYMGPU_READBACK_PLAIN=1 makes every one of them a copy + stream synchronisation.
     Product + cleanup, a rotation with duplicate rows (multi-launch path), GF(2) elimination, a projection: same results both ways."""
     rng = np.random.default_rng(77)
     n = 40

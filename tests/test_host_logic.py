@@ -460,14 +460,14 @@ def test_every_entry_point_takes_its_context_lock():
 def test_lock_scan_names_an_entry_point_that_drops_its_lock_and_a_stale_allowlist():
     sources = _hip_sources()
     # SG_ENTER removed from one entry point: the scan names it
-    fname = 'context.hip'
+    fname = 'op_handles.hip'
     body = _entry_point_bodies(sources[fname])['symgpu_op_scale']
     assert body.count('SG_ENTER(op);') == 1
     start = sources[fname].index('int symgpu_op_scale(')
     broken = dict(sources)
     broken[fname] = sources[fname][:start] + sources[fname][start:].replace('SG_ENTER(op);', 'SG_TRY(require_ctx());', 1)
     problems, _ = _lock_violations(broken, UNLOCKED_ENTRY_POINTS)
-    assert len(problems) == 1 and problems[0].startswith('symgpu_op_scale (context.hip) takes no context lock'), problems
+    assert len(problems) == 1 and problems[0].startswith('symgpu_op_scale (op_handles.hip) takes no context lock'), problems
     # a name taken off the allowlist: the scan names it
     allow = dict(UNLOCKED_ENTRY_POINTS)
     del allow['symgpu_comm_barrier']
