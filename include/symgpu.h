@@ -84,7 +84,11 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * guard bytes were overwritten (tuning build, SYMGPU_ALLOC_CANARY); 12: the most threads seen using one device's context at once since
  * load, counted where a call uses the context's state, whichever lock it took (1 while the per-device lock holds); 13: calls that found
  * their device busy with another thread's call and waited; 14: uses of a device's context by a call that did not hold that context's
- * lock (0 while the lock is taken on the right device). */
+ * lock (0 while the lock is taken on the right device).  15: blocks (of up to 64 rows) panelled by the blocked GF(2) elimination since
+ * load — the one-workgroup path for matrices of at most 64 rows and 64 words counts none; 16: of these, the blocks whose panel ran on the
+ * full rows in LDS; 17: of these, the blocks whose panel ran on the two-word window (the rest took the four-word window, or held zero rows
+ * only).  A reduction that is redone after an in-launch time-out counts both runs.  tests/test_gpu_gf2_structure.py asserts through
+ * them which panel a matrix family took. */
 int symgpu_debug_counter(int which, int64_t *value);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so

@@ -223,6 +223,7 @@ __device__ __forceinline__ void panel_wave(const u64 *__restrict__ rows, i64 R, 
     int pw = -1, pb = 0;                                            // this lane's (= block row's) pivot
     u64 my_mask = 0;                                                // mask_j for j = lane
     u64 tv = 1ULL << lane;                                          // T row of this lane
+    bool narrow_ran = false;
     if (fin_m != 0) {
         const int jf = __builtin_ctzll(fin_m);
         const int w_lo = window_start(a, valid, jf);
@@ -231,6 +232,7 @@ __device__ __forceinline__ void panel_wave(const u64 *__restrict__ rows, i64 R, 
         // A row that cancels to zero inside the two words ends the block (as it does with four), so the result is unchanged.
         const bool narrow = __ballot(valid && a != NOLEAD && !(a >= w_lo && a < w_lo + 2)) == 0ULL;
         const int wn = narrow ? 2 : WN;
+        narrow_ran = narrow;
         const u64 in_m = __ballot(valid && a != NOLEAD && a >= w_lo && a < w_lo + wn);
         const u64 todo0 = (n_valid >= 64 ? ~0ULL : ((1ULL << n_valid) - 1ULL)) & ~zero_m;
         static_assert(WN >= 2, "narrow window");
@@ -238,6 +240,8 @@ __device__ __forceinline__ void panel_wave(const u64 *__restrict__ rows, i64 R, 
         else if (narrow) panel_loop<2>(rows, Wc, i0, lane, valid, w_lo, in_m, todo0, kk, pw, pb, my_mask, tv, spec, w_spec, w_max);
         else panel_loop<WN>(rows, Wc, i0, lane, valid, w_lo, in_m, todo0, kk, pw, pb, my_mask, tv, spec, w_spec, w_max);
     }
+    // block statistics {blocks | two-word windows << 32}: one add per block, issued ahead of the publication so that nothing waits behind it
+    if (lane == 0 && kk > 0) atomicAdd(xor_count + 2, 1ULL | ((unsigned long long)narrow_ran << 32));
     // publish: only rows < kk belong to the block
     const u64 low = (kk >= 64) ? ~0ULL : ((1ULL << kk) - 1ULL);
     const bool mine = lane < kk;
@@ -274,6 +278,7 @@ __device__ __forceinline__ void panel_full(const u64 *__restrict__ rows, i64 R, 
     __syncthreads();
     int pw = -1, pb = 0;                                            // wavefront 0, lane = block row
     u64 my_mask = 0, tv = 1ULL << lane;
+    if (threadIdx.x == 0) atomicAdd(xor_count + 2, 1ULL);           // block statistics: a block (the full-row ones are counted where the choice is made)
     for (int j = 0; j < n_valid; ++j) {
         if (wave == 0) {
             int jw = -1, jb = 0;
@@ -736,11 +741,11 @@ static int rref_dev_impl(u64 *rows, i64 R, i64 Wc, i64 *xor_count, i64 *pivots_h
     SG_TRY(lead.alloc(WK * sizeof(int)));
     SG_TRY(sel.alloc((size_t)R * 8));
     SG_TRY(snap.alloc((size_t)WK * Wc * 8));
-    SG_TRY(count.alloc(16));
+    SG_TRY(count.alloc(32));                                        // {XOR count, time-out flag | full-row panels << 32, blocks | two-word windows << 32, -}
     SG_TRY(piv.alloc((size_t)R * 8));
     SG_TRY(rowcnt.alloc((size_t)R * 4));
     HIP_TRY(hipMemsetAsync(rowcnt.p, 0, (size_t)R * 4, st));
-    HIP_TRY(hipMemsetAsync(count.p, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(count.p, 0, 32, st));
     SG_TRY(ready.alloc(2 * WK * sizeof(u64)));
     HIP_TRY(hipMemsetAsync(ready.p, 0, 2 * WK * sizeof(u64), st));
     HIP_TRY(hipMemsetAsync(state.p, 0, sizeof(SweepState), st));
@@ -845,17 +850,20 @@ static int rref_dev_impl(u64 *rows, i64 R, i64 Wc, i64 *xor_count, i64 *pivots_h
     }
     hipLaunchKernelGGL(k_sum_u32, dim3(256), dim3(256), 0, st, rowcnt.as<u32>(), R, count.as<unsigned long long>());
     KERNEL_CHECK();
-    unsigned long long hb[2] = {0, 0};
+    unsigned long long hb[3] = {0, 0, 0};
     if (pivots_host) {
-        HIP_TRY(hipMemcpyAsync(hb, count.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hb, count.p, 24, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(pivots_host, piv.p, (size_t)R * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     } else {
-        u32 w[4] = {0, 0, 0, 0};
-        SG_TRY(read_back_words(reinterpret_cast<const u32 *>(count.p), 4, nullptr, 0, w));
-        hb[0] = ((unsigned long long)w[1] << 32) | w[0];
-        hb[1] = ((unsigned long long)w[3] << 32) | w[2];
+        u32 w[6] = {0, 0, 0, 0, 0, 0};
+        SG_TRY(read_back_words(reinterpret_cast<const u32 *>(count.p), 6, nullptr, 0, w));
+        for (int k = 0; k < 3; ++k) hb[k] = ((unsigned long long)w[2 * k + 1] << 32) | w[2 * k];
     }
+    // which panel the blocks of this run took (symgpu_debug_counter 15 / 16 / 17; a run that is redone after a time-out counts twice)
+    bump_counter(15, (i64)(u32)hb[2]);
+    bump_counter(16, (i64)(u32)(hb[1] >> 32));
+    bump_counter(17, (i64)(u32)(hb[2] >> 32));
     if (SG_TUNE("SYMGPU_GF2_DEBUG")) fprintf(stderr, "rref %lld x %lld words: full-row panels %u\n", (long long)R, (long long)Wc, (u32)(hb[1] >> 32));
     if ((u32)hb[1] != 0) { *timed_out = true; return SYMGPU_OK; }
     if (xor_count) *xor_count = (i64)hb[0];

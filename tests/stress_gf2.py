@@ -1,11 +1,14 @@
 # randomised cross-check of the GF(2) elimination schedules (run on the GPU box): default against SYMGPU_GF2_FULL_PANEL=0,
 # SYMGPU_GF2_FUSED_SELECT=0, SYMGPU_GF2_LOOKAHEAD=0, SYMGPU_GF2_SMALL=0 and — for small matrices — the NumPy restatement of the
-# reference loop; random, sparse, banded, low-rank, duplicate-row and zero-row matrices
+# reference loop; the matrix kinds are the families of tests/_gf2_families.py (the ones tests/test_gpu_gf2_structure.py runs at fixed
+# sizes), here at random sizes, densities, steps and band widths
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from symmer_amd import kernels, packing
 from oracle import oracle_np as onp
+import _gf2_families as fam
+VARIANTS = fam.variants()
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 n_cases = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 rng = np.random.default_rng(seed)
@@ -16,24 +19,12 @@ for case in range(n_cases):
     R = int(rng.choice([1, 2, 63, 64, 65, 100, 129, 300, 700, 1500, 2500]))
     C = int(rng.choice([1, 5, 64, 65, 200, 700, 3000, 9000, 16384, 16400, 30000]))
     if R * C > 3e7: C = int(3e7 // R)
-    kind = int(rng.integers(0, 6))
     dens = float(rng.choice([0.001, 0.003, 0.02, 0.2, 0.5]))
-    m = rng.random((R, C)) < dens
-    if kind == 1:                                            # banded: every row leads near its index
-        m[:] = False
-        for r in range(R):
-            c0 = min(C - 1, (r * C) // max(1, R)); w = min(C - c0, int(rng.integers(1, 40)))
-            m[r, c0:c0 + w] = rng.random(w) < 0.6
-    elif kind == 2:                                          # low rank: rows are XORs of a few basis rows
-        k = max(1, min(R, 20)); basis = rng.random((k, C)) < max(dens, 0.02)
-        m = (rng.integers(0, 2, (R, k)) @ basis.astype(np.int64)) % 2 == 1
-    elif kind == 3:                                          # duplicates and zero rows
-        m[rng.integers(0, R, max(1, R // 3))] = m[rng.integers(0, R, max(1, R // 3))]
-        m[rng.integers(0, R, max(1, R // 5))] = False
-    elif kind == 4:                                          # identity-like with noise on the right (the symmetry matrices' shape)
-        m[:] = False
-        for r in range(min(R, C)): m[r, r] = True
-        if C > R: m[:, R:] = rng.random((R, C - R)) < dens
+    kind, fn, kw = VARIANTS[int(rng.integers(0, len(VARIANTS)))]
+    if fn in (fam.dense, fam.low_rank, fam.identity_plus_noise): kw = dict(kw, density=max(dens, 0.02) if fn is fam.low_rank else dens)
+    elif fn in (fam.staircase, fam.reverse_staircase): kw = dict(kw, step=int(rng.choice([1, 3, 67, 129, 300])))
+    elif fn is fam.banded: kw = dict(kw, slope=None if rng.random() < 0.5 else kw['slope'], width=int(rng.integers(1, 40)))
+    m = fn(rng, R, C, **kw)
     packed = packing.pack_bits(m)
     outs = []
     for env in ENVS:
