@@ -667,11 +667,12 @@ def refusal_cases():
         ('mul_allpairs_dev/Wq-mismatch', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.a, I64(0), I64(1), 1, o.w1)),
         ('mul_allpairs_dev/outer-range', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.a, I64(0), I64(13), 1, o.b)),
         ('mul_allpairs_dev/null-out', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.a, I64(0), I64(1), 1, None)),
-        # gf2.hip
+        # gf2_driver.hip
         ('rref/negative-R', 'rref', lambda L, o: L.symgpu_rref(R(o), I64(-1), I64(4), None, None)),
         ('rref/null-rows', 'rref', lambda L, o: L.symgpu_rref(None, I64(12), I64(4), None, None)),
         ('rref_dev/negative-Wc', 'rref_dev', lambda L, o: L.symgpu_rref_dev(o.dev, I64(4), I64(-1), None, None)),
         ('rref_dev/null-rows', 'rref_dev', lambda L, o: L.symgpu_rref_dev(None, I64(4), I64(4), None, None)),
+        # gf2_symmetry.hip
         ('symmetry_kernel/n-does-not-match-Wq', 'symmetry_kernel', lambda L, o: L.symgpu_symmetry_kernel(R(o), I64(12), 100, 1, B, I64(8), byref(n64), None)),
         ('symmetry_kernel/null-k', 'symmetry_kernel', lambda L, o: L.symgpu_symmetry_kernel(R(o), I64(12), 100, 2, B, I64(8), None, None)),
         ('symmetry_kernel/null-H', 'symmetry_kernel', lambda L, o: L.symgpu_symmetry_kernel(None, I64(12), 100, 2, B, I64(8), byref(n64), None)),

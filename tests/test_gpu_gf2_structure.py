@@ -138,7 +138,7 @@ def test_staircase_long_rows_take_the_four_word_window_and_end_early(R, monkeypa
 @pytest.mark.parametrize('R,C', [(700, 16384), (700, 16448), (129, 4160), (64, 20000)])
 def test_dense_takes_windows_and_whole_blocks(R, C, density, monkeypatch):
     """Bound on the blocks of a dense matrix.  (a) A block that neither ends early nor is the last takes 64 rows, so with E early ends
-    there are at most R // 64 + 1 + E blocks.  (b) window_start (gf2.hip:80-90) puts the window at the smallest leading word of the block's
+    there are at most R // 64 + 1 + E blocks.  (b) window_start (gf2_panel.h) puts the window at the smallest leading word of the block's
     rows: in a dense matrix, the word of the pivot frontier (the first column that is no pivot yet).  The window holds at least 128
     columns from the start of that word and the 64 pivots of a block move the frontier by 64 columns and the few a random row skips, so
     a block can only run out of window when the frontier entered it in the upper part of its word — and the block after such an end
@@ -243,6 +243,35 @@ def test_injected_time_out_on_structured_matrices(name, R, C, monkeypatch):
     assert once > 0 and twice == 2 * once, f'the injected run panelled {twice} blocks, a plain run {once}: it did not run twice'
     assert _lib.degraded() == degraded, 'the injected time-out was reported as a degraded fast path'
     assert not any('GF(2)' in d for d in _lib.degraded())
+
+
+@pytest.mark.parametrize('name', ['dense-density0.5', 'staircase-step67'])
+@pytest.mark.parametrize('R,C', [(64, 4096), (33, 64)])
+def test_injected_time_out_on_a_small_matrix_sent_through_the_blocked_path(name, R, C, monkeypatch):
+    """SYMGPU_GF2_SMALL=0 sends a matrix of <= 64 rows and <= 64 words through the fused blocked schedule: plan_rref decides path and
+    schedule in one place, so the matrix gets its safety copy and SYMGPU_GF2_FUSED_SELECT=2 reaches it like any other (restore, second
+    run with separate launches: counter 15 rises by twice a plain blocked run's).  Nothing is latched or reported, and the next plain
+    call takes the one-workgroup path again.  (Before the plan existed, the copy and the injection were decided from the size alone
+    and the injection was ignored here: counter 15 rose once.)"""
+    p, expect = case(name, R, C)
+    assert R <= 64 and p.shape[1] <= 64
+    degraded = _lib.degraded()
+    set_schedule(monkeypatch, {'SYMGPU_GF2_SMALL': '0'})
+    before = counters()
+    assert_rref(p, expect, f'{name} {R}x{C} [no_small]')
+    once = (counters() - before)[0]
+    set_schedule(monkeypatch, {'SYMGPU_GF2_SMALL': '0', 'SYMGPU_GF2_FUSED_SELECT': '2'})
+    before = counters()
+    assert_rref(p, expect, f'{name} {R}x{C} [no_small, injected time-out]')
+    twice = (counters() - before)[0]
+    print(f'{name} {R}x{C}: {once} blocks plain, {twice} with the injected time-out')
+    assert once > 0 and twice == 2 * once, f'the injected run panelled {twice} blocks, a plain blocked run {once}: it did not run twice'
+    assert _lib.degraded() == degraded, 'the injected time-out was reported as a degraded fast path'
+    assert not any('GF(2)' in d for d in _lib.degraded())
+    set_schedule(monkeypatch, {})
+    before = counters()
+    assert_rref(p, expect, f'{name} {R}x{C} [after the injection]')
+    assert tuple(counters() - before) == (0, 0, 0), 'the next plain call did not take the one-workgroup path'
 
 
 # ---------------------------------------------------------------- 5. symgpu_rref_dev --------------------------------------------
