@@ -260,7 +260,7 @@ int bits_to_bytes_dev(const u64 *bits, i64 stride_words, i64 N, i64 M, uint8_t *
 // commute_m4r7.hip — the same product with two 7-bit tables per step (called by commutes_m4r_dev, which owns the operand preparation of B)
 int commutes_m4r7_launch(const u64 *A, i64 N, i64 M, int Wq, const u64 *bt_p, i64 Mw_pad, int R, bool bytes, void *dst, i64 stride);
 
-// product.hip
+// product.hip, product_pairs.hip, product_driver.hip (what they share among themselves: product_common.h)
 // ---- shared device helpers ----------------------------------------------------------------------
 // exact phase application: multiply (re, im) by i^e
 __device__ __forceinline__ void apply_phase(double re, double im, int e, double &ore, double &oim) {
@@ -313,7 +313,6 @@ struct PairKeyArgs {
 
 int mul_coeff_dev(const u64 *inner, const double *ci, i64 Ni, const u64 *outer, const double *co, i64 o_begin, i64 o_end,
                   int Wq, int inner_is_left, double *out_coeff);
-int mul_rows_dev(const u64 *inner, i64 Ni, const u64 *outer, i64 o_begin, i64 o_end, int Wq, u64 *out_rows);
 // packed (hash | phase exponent | o | i) keys of all pairs, for the fused product + cleanup
 int mul_keys_dev(const u64 *inner, i64 Ni, const u64 *outer, i64 No, int Wq, int inner_is_left, PairKeyArgs ka);
 

@@ -1,7 +1,9 @@
 """GPU: the coefficient stage of the phase-sum product path (product.hip k_mul_rows_e + k_mul_coeff_expand), bit-exact against the C
 oracle.  The row kernel leaves the 2-bit phase sum of every pair, four pairs to a byte; the expansion writes one 256-term piece of one
 outer row per workgroup.  The shapes below end packed bytes and 256-term pieces part-full, cut the inner operand into tiles, need more
-outer rows than one launch's grid.y holds, and write a slab with o_begin > 0 into an output handle that already holds another slab."""
+outer rows than one launch's grid.y holds, and write a slab with o_begin > 0 into an output handle that already holds another slab.
+The slab and grid.y cases also run with the switches that select the other paths of the product (word-major or wide coefficient kernel
+followed by the plain row stream, rows only): each path has its own o_begin and batch-offset arithmetic."""
 import numpy as np
 import pytest
 from symmer_amd import kernels, packing, _lib
@@ -55,20 +57,33 @@ def test_coeff_stage_inner_tiles(n, monkeypatch):
     check_pairs(np.random.default_rng(1100 + n), n, Ni, 3, n % 2 == 0)
 
 
-def test_coeff_stage_more_outer_rows_than_one_grid():
-    """70,000 outer rows: more than the 65,535 of one launch's grid.y, so the slab goes out in two launches of each kernel."""
+@pytest.mark.parametrize('fused', ['1', '0'])
+def test_coeff_stage_more_outer_rows_than_one_grid(fused, monkeypatch):
+    """70,000 outer rows: more than the 65,535 of one launch's grid.y, so the slab goes out in two launches of each kernel (fused = 0: of
+    the plain row stream, behind the word-major coefficient kernel)."""
+    monkeypatch.setenv('SYMGPU_PRODUCT_FUSED', fused)
     check_pairs(np.random.default_rng(1200), 20, 3, 70000, True)
 
 
-@pytest.mark.parametrize('n,Ni', [(1000, 257), (40, 1025), (4090, 5)])
-def test_coeff_stage_slab_into_reused_handle(n, Ni):
-    """A slab [o_begin, o_end) with o_begin > 0 written into an output handle that already holds a longer slab of the same product."""
+# the paths of symgpu_mul_allpairs_dev by environment: phase-byte stream where the row length allows it / word-major coefficient kernel +
+# plain row stream / wide coefficient kernel + plain row stream
+PATH_ENVS = [{}, {'SYMGPU_PRODUCT_FUSED': '0'}, {'SYMGPU_PRODUCT_FUSED': '0', 'SYMGPU_WIDE': '1'}]
+
+
+@pytest.mark.parametrize('env', PATH_ENVS, ids=['default', 'fused0', 'fused0-wide1'])
+@pytest.mark.parametrize('n,Ni', [(1000, 257), (40, 1025), (4090, 5), (300, 257)])
+def test_coeff_stage_slab_into_reused_handle(n, Ni, env, monkeypatch):
+    """A slab [o_begin, o_end) with o_begin > 0 written into an output handle that already holds a longer slab of the same product; the
+    same slabs into a handle without coefficients (rows only).  n = 300 is 5 chunks per row: the word-major path even in the default environment."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
     rng = np.random.default_rng(1300 + n + Ni)
     No = 9
     a = packing.pack_rows(rng.random((Ni, 2 * n)) < 0.3); b = packing.pack_rows(rng.random((No, 2 * n)) < 0.3)
     ca, cb = gaussian(rng, Ni), gaussian(rng, No)
     A, B = DeviceOp.upload(a, ca), DeviceOp.upload(b, cb)
     out = DeviceOp.alloc(No * Ni, (n + 63) // 64, with_coeff=True)
+    out_rows = DeviceOp.alloc(No * Ni, (n + 63) // 64, with_coeff=False)
     lib = _lib.lib()
     try:
         for o0, o1 in ((0, No), (4, 7), (8, 9)):
@@ -77,6 +92,9 @@ def test_coeff_stage_slab_into_reused_handle(n, Ni):
             rows, coeff = out.download()
             er, ec = oc.mul_allpairs(a, ca, b[o0:o1], cb[o0:o1], True)
             assert np.array_equal(rows, er) and np.array_equal(coeff, ec), (o0, o1)
+            _lib.check(lib.symgpu_mul_allpairs_dev(A.handle, B.handle, o0, o1, 1, out_rows.handle))
+            assert out_rows.n_terms == (o1 - o0) * Ni
+            assert np.array_equal(out_rows.download(with_coeff=False), er), (o0, o1, 'rows only')
     finally:
-        for h in (A, B, out):
+        for h in (A, B, out, out_rows):
             h.free()
