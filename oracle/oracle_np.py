@@ -342,7 +342,13 @@ def check_adjmat_noncontextual(adjmat):
     restricted to those terms have to be disjoint."""
     adjmat = np.asarray(adjmat, dtype=bool)
     non_universal = np.where(~np.all(adjmat, axis=1))[0]
-    unique_rows = np.unique(adjmat[non_universal, :][:, non_universal], axis=0)
+    sub = np.ascontiguousarray(adjmat[non_universal, :][:, non_universal])
+    if sub.size == 0:
+        return True
+    # np.unique(sub, axis=0), each row taken as one opaque key: the axis form sorts a record of one field per column, far slower on
+    # thousands of long, mostly equal rows; the set of unique rows is the same
+    keys = sub.view(np.dtype((np.void, sub.shape[1]))).ravel()
+    unique_rows = sub[np.unique(keys, return_index=True)[1]]
     return bool(np.all(np.count_nonzero(unique_rows, axis=0) == 1))
 
 
