@@ -88,7 +88,11 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * load — the one-workgroup path for matrices of at most 64 rows and 64 words counts none; 16: of these, the blocks whose panel ran on the
  * full rows in LDS; 17: of these, the blocks whose panel ran on the two-word window (the rest took the four-word window, or held zero rows
  * only).  A reduction that is redone after an in-launch time-out counts both runs.  tests/test_gpu_gf2_structure.py asserts through
- * them which panel a matrix family took. */
+ * them which panel a matrix family took.  18 / 19: commutation calls (symgpu_commutes, symgpu_commutes_dev, symgpu_commutes_bits_dev and
+ * what is built on them) served by the register-tile kernel / by the wide-row kernel; 20 / 21: launches of the Four-Russians commutation
+ * kernel with one tile per workgroup / as stream-K (persistent workgroups over the (tile, step) space; a stream-K request with fewer tiles
+ * than compute units counts as 20).  A call with no rows on either side counts nothing.  tests/test_gpu_commute_families.py asserts
+ * through them which kernel a call took. */
 int symgpu_debug_counter(int which, int64_t *value);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so

@@ -183,7 +183,9 @@ static bool use_m4r(i64 N, i64 M, int Wq) {
 int commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner) {
     if (N == 0 || M == 0) return SYMGPU_OK;
     if (use_m4r(N, M, Wq)) return commutes_m4r_dev(A, N, B, M, Wq, out, out_bits, b_owner);
-    if (wide_pairs_worthwhile(N, M, Wq)) return wide_commutes_dev(A, N, B, M, Wq, out, out_bits);      // few pairs of very long rows
+    // which kernel served the call: symgpu_debug_counter 18 (register tile) / 19 (wide rows); the Four-Russians launches count themselves (20 / 21)
+    if (wide_pairs_worthwhile(N, M, Wq)) { bump_counter(19); return wide_commutes_dev(A, N, B, M, Wq, out, out_bits); }      // few pairs of very long rows
+    bump_counter(18);
     const int W = 2 * Wq;
     const int cj = DJ;
     const bool same = (B == A && M == N);                 // adjacency: one word-major copy serves both sides

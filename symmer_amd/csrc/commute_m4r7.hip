@@ -582,6 +582,7 @@ static int launch_m7s(const uint8_t *A7, i64 Npad, i64 N, const u64 *BT, i64 Mw_
     bool stream = n_tiles >= P && max_steps >= M7_STREAM_MIN_STEPS && n_tiles * max_steps >= (i64)M7_STREAM_MIN_WORK * P;
     if (const char *e = getenv("SYMGPU_M4R_STREAM")) stream = n_tiles >= P && atoi(e) != 0;
     const int force_fixup = getenv("SYMGPU_M4R_FIXUP") ? 1 : 0;
+    bump_counter(stream ? 21 : 20);                                   // which launch this is (symgpu_debug_counter 20 / 21)
     Scratch part, dbgbuf;
     Context &c = ctx();
     if (!c.m7_flags) {                                                // [P] "head part published" + [P] "tile left to the fix-up launch", compared with the launch's epoch

@@ -1070,7 +1070,9 @@ def test_commutes_bit_packed_output(n, N, M):
 def test_commutes_both_kernels(n, N, M, dens, force, monkeypatch):
     """The Four-Russians kernel (commute_m4r.hip: LDS tables, SYMGPU_COMMUTE_M4R=1) and the register-tile kernel (=0) on
     the same ragged shapes — row counts around the 512/768/1280-row workgroup tiles, column counts around the 2048-column
-    tile and the 64-bit word, a sparse operand (most k-blocks skipped), N = 1 and M = 1 — bytes and bit-packed output."""
+    tile and the 64-bit word, a sparse operand (density 0.01: over 1,300 rows every 7-bit group of the left operand is still non-zero, so
+    no step is skipped — tests/test_gpu_commute_families.py runs left operands that live in a few groups), N = 1 and M = 1 — bytes and
+    bit-packed output."""
     import ctypes
     from symmer_amd import _lib
     from symmer_amd.kernels import DeviceOp
@@ -1110,17 +1112,23 @@ def test_commutes_m4r_tile_heights(r, M, monkeypatch):
     assert np.array_equal(kernels.commutes(a, b), expect)
 
 
-@pytest.mark.parametrize('force', ['1', '0'])
+@pytest.mark.parametrize('force', ['1', '0', '1-unfused'])
 @pytest.mark.parametrize('N,M,off', [(700, 2500, 3), (513, 1001, 8), (300, 15, 13), (64, 7, 1), (1100, 4099, 0), (5, 3, 5)])
 def test_commutes_any_row_length_any_alignment(N, M, off, force, monkeypatch):
-    """np.bool_ tables whose rows are not multiples of 16 (8) bytes, or whose base is not aligned, are computed as bit-packed rows and
-    written by the flat 16-byte expansion (commute_m4r.hip k_bits_to_bytes_flat: chunks that run over a row end, rows shorter than a
-    chunk, unaligned head and tail) — both commutation kernels, output at `off` bytes into a device buffer whose other bytes must
-    stay untouched."""
+    """np.bool_ tables whose rows are not multiples of 16 (8) bytes, or whose base is not aligned, output at `off` bytes into a device
+    buffer whose other bytes must stay untouched.  Mode '1': the Four-Russians kernel's own byte epilogue (commute_m4r7.hip m7_store16:
+    unaligned 16-byte stores, the columns past a row's last whole chunk byte by byte — the default since round 6); mode '0': the
+    register-tile kernel's unaligned 8-byte stores; mode '1-unfused' (SYMGPU_M4R_UNFUSED=1): the Four-Russians kernel writes bit-packed
+    rows to scratch and the flat 16-byte expansion writes the table (commute_m4r.hip k_bits_to_bytes_flat: chunks that run over a row
+    end, rows shorter than a chunk, unaligned head and tail)."""
     import ctypes
     from symmer_amd import _lib
     from symmer_amd.kernels import DeviceOp
-    monkeypatch.setenv('SYMGPU_COMMUTE_M4R', force)
+    monkeypatch.setenv('SYMGPU_COMMUTE_M4R', force[0])
+    if force == '1-unfused':
+        monkeypatch.setenv('SYMGPU_M4R_UNFUSED', '1')
+    else:
+        monkeypatch.delenv('SYMGPU_M4R_UNFUSED', raising=False)
     rng = np.random.default_rng(400 + N + M)
     n = 130
     a = packing.pack_rows(rng.random((N, 2 * n)) < 0.3); b = packing.pack_rows(rng.random((M, 2 * n)) < 0.3)
