@@ -130,8 +130,8 @@ extern std::atomic<i64> g_counters[22];    // debug counters (symgpu_debug_count
                                            // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
                                            // [14] uses of a context by a call that did not hold its lock, [15] blocks panelled by the blocked GF(2)
                                            // elimination, [16] / [17] of these: on the full rows in LDS / on the two-word window (gf2.hip),
-                                           // [18] / [19] commutation calls served by the register-tile / the wide-row kernel (commute.hip), [20] / [21]
-                                           // Four-Russians commutation launches with one tile per workgroup / stream-K (commute_m4r7.hip)
+                                           // [18] / [19] commutation calls served by the register-tile / the wide-row kernel, [20] / [21] Four-Russians
+                                           // commutation launches with one tile per workgroup / stream-K (commute_driver.hip, one place each)
 inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
 inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
 inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }
@@ -251,16 +251,11 @@ const u32 *radix_sort_coop_flag();
 void radix_sort_coop_note(u32 flag, bool *timed_out);
 int radix_sort_coop_check(bool *timed_out);     // after a stream synchronisation: did a one-launch sort give up (output invalid)?
 
-// commute.hip
+// commute_driver.hip (what the commutation files share among themselves: commute_common.h)
 // b_owner (may be null): the operator B's rows belong to (all of them), so that per-operand layouts can be cached on it
 int commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner = nullptr);
+// ycount.hip
 int ycount_dev(const u64 *rows, i64 T, int Wq, int *out);
-// commute_m4r.hip — the same contract on the Four-Russians kernel (LDS tables)
-int commutes_m4r_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner = nullptr);
-bool commutes_m4r_worthwhile(i64 N, i64 M);
-int bits_to_bytes_dev(const u64 *bits, i64 stride_words, i64 N, i64 M, uint8_t *out);   // bit-packed rows -> np.bool_ [N][M], any M, any alignment
-// commute_m4r7.hip — the same product with two 7-bit tables per step (called by commutes_m4r_dev, which owns the operand preparation of B)
-int commutes_m4r7_launch(const u64 *A, i64 N, i64 M, int Wq, const u64 *bt_p, i64 Mw_pad, int R, bool bytes, void *dst, i64 stride);
 
 // product.hip, product_pairs.hip, product_driver.hip (what they share among themselves: product_common.h)
 // ---- shared device helpers ----------------------------------------------------------------------

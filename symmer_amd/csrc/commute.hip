@@ -1,5 +1,5 @@
 // commute.hip — termwise commutation / adjacency (reference: symmer/operators/base.py:938-971 via
-// matmul_GF2, utils.py:9-78) and Y_count (base.py:604-615).
+// matmul_GF2, utils.py:9-78): the register-tile kernel and its launch wrapper.  Which calls it serves: plan_commutes, commute_driver.hip.
 //
 //   C[i][j] = NOT parity( |x_i & z'_j| + |z_i & x'_j| )      (True = commute)
 //
@@ -13,8 +13,7 @@
 // s_load_dwordx16 (wave-uniform address) and are copied to VGPRs, every lane owns 8 ADJACENT columns of B
 // (64 contiguous bytes per word) and keeps 8x8 32-bit XOR accumulators in VGPRs.  No LDS is needed:
 // nothing is shared between lanes.
-#include "common.h"
-#include <stdlib.h>
+#include "commute_common.h"
 #include <stdint.h>
 
 namespace symgpu {
@@ -124,104 +123,27 @@ __global__ __launch_bounds__(256) void k_commutes(const u64 *__restrict__ At, i6
     }
 }
 
-// Y_count: one lane group per row on row-major packed rows (tiny, O(T*Wq))
-__global__ void k_ycount(const u64 *__restrict__ rows, i64 T, int Wq, int *__restrict__ out) {
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (i64)gridDim.x * blockDim.x) {
-        const u64 *r = rows + t * 2 * Wq;
-        int c = 0;
-        for (int w = 0; w < Wq; ++w) c += __popcll(r[w] & r[Wq + w]);
-        out[t] = c;
-    }
-}
+static_assert(CI * WAVES == RT_BLOCK_ROWS && 64 * DJ == RT_BLOCK_COLS, "the plan pads the operands to whole workgroups");
 
-// long rows: one block per row, the words spread over its threads (one thread walking 1.5 million words took 0.2 s)
-__global__ __launch_bounds__(256) void k_ycount_long(const u64 *__restrict__ rows, i64 t_base, int Wq, int *__restrict__ out) {
-    __shared__ int red[4];
-    const i64 t = t_base + blockIdx.x;
-    const u64 *r = rows + t * 2 * Wq;
-    int c = 0;
-    for (int w = threadIdx.x; w < Wq; w += 256) c += __popcll(r[w] & r[Wq + w]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) out[t] = red[0] + red[1] + red[2] + red[3];
-}
-
-int ycount_dev(const u64 *rows, i64 T, int Wq, int *out) {
-    if (T == 0) return SYMGPU_OK;
-    if (Wq >= 512) {
-        for (i64 t0 = 0; t0 < T; t0 += 0x7fffffff) {
-            const i64 nt = T - t0 < 0x7fffffff ? T - t0 : 0x7fffffff;
-            hipLaunchKernelGGL(k_ycount_long, dim3((unsigned)nt), dim3(256), 0, ctx().stream, rows, t0, Wq, out);
-            KERNEL_CHECK();
-        }
-        return SYMGPU_OK;
-    }
-    int grid = (int)((T + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(k_ycount, dim3(grid), dim3(256), 0, ctx().stream, rows, T, Wq, out);
-    KERNEL_CHECK();
-    return SYMGPU_OK;
-}
-
-static i64 round_up(i64 x, i64 m) { return (x + m - 1) / m * m; }
-
-// A: N rows, B: M rows, row-major packed device pointers.  Exactly one of out / out_bits is non-null.
-// Which kernel: the Four-Russians kernel (commute_m4r.hip) does 1/16 of the VALU work per pair but pays a fixed price per
-// workgroup (operand transposes, 64 KiB table per k-block shared by >= 512 rows), so it needs enough rows and columns to fill
-// the chip with its 512..1536 x 2048 tiles; the register-tile kernel below serves everything smaller.  SYMGPU_COMMUTE_M4R=1 / 0 forces
-// one or the other (the tests run both on every case).
-static bool use_m4r(i64 N, i64 M, int Wq) {
-    if (const char *e = getenv("SYMGPU_COMMUTE_M4R")) {
-        if (e[0] == '1') return true;
-        if (e[0] == '0') return false;
-    }
-    return commutes_m4r_worthwhile(N, M);
-}
-
-int commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner) {
-    if (N == 0 || M == 0) return SYMGPU_OK;
-    if (use_m4r(N, M, Wq)) return commutes_m4r_dev(A, N, B, M, Wq, out, out_bits, b_owner);
-    // which kernel served the call: symgpu_debug_counter 18 (register tile) / 19 (wide rows); the Four-Russians launches count themselves (20 / 21)
-    if (wide_pairs_worthwhile(N, M, Wq)) { bump_counter(19); return wide_commutes_dev(A, N, B, M, Wq, out, out_bits); }      // few pairs of very long rows
-    bump_counter(18);
-    const int W = 2 * Wq;
-    const int cj = DJ;
-    const bool same = (B == A && M == N);                 // adjacency: one word-major copy serves both sides
-    const i64 Mpad = round_up(M, 64 * cj), Npad = same ? Mpad : round_up(N, CI * WAVES);
-    Scratch at, bt;
-    SG_TRY(at.alloc((size_t)Npad * W * sizeof(u64)));
-    SG_TRY(to_wordmajor(A, N, W, at.as<u64>(), Npad));
-    const u64 *Bt = nullptr;
-    if (B == A && M == N && Mpad == Npad) {
-        Bt = at.as<u64>();
-    } else {
-        SG_TRY(bt.alloc((size_t)Mpad * W * sizeof(u64)));
-        SG_TRY(to_wordmajor(B, M, W, bt.as<u64>(), Mpad));
-        Bt = bt.as<u64>();
-    }
+int launch_register_tile(const CommutePlan &pl, const u64 *At, i64 N, const u64 *Bt, i64 M, int Wq, uint8_t *out, u64 *out_bits) {
     // blockIdx.x walks along i (fast) so that consecutive blocks reuse the same B column tile from L2
-    const i64 gx = Npad / (CI * WAVES), gy = Mpad / (64 * cj);
     // np.bool_ output: 8-byte stores whatever the row length and the base address (unaligned where they have to be; the last columns of a
     // row that do not fill a lane's 16 go out byte by byte).  Round 6: rows that are not a multiple of 8 bytes used to be written byte by
     // byte altogether — 0.083 ms for a 10,001^2 table against 0.041 ms for 10,000^2.
-    u64 *bits_dst = out_bits;
-    const i64 Mw = (M + 63) / 64;
+    const i64 stride_bytes = (M + 63) / 64 * 8;
     // grid.y is limited to 65535: loop over column super-tiles if needed
     const i64 max_gy = 65535;
-    for (i64 y0 = 0; y0 < gy; y0 += max_gy) {
-        i64 ny = gy - y0 < max_gy ? gy - y0 : max_gy;
-        const i64 joff = y0 * 64 * cj;
-        dim3 grid((unsigned)gx, (unsigned)ny);
+    for (i64 y0 = 0; y0 < pl.gy_total; y0 += max_gy) {
+        const i64 ny = pl.gy_total - y0 < max_gy ? pl.gy_total - y0 : max_gy;
+        const i64 joff = y0 * RT_BLOCK_COLS;
+        dim3 grid((unsigned)pl.gx, (unsigned)ny);
         ProfScope prof(1);
-        if (bits_dst) {
-            const i64 stride_bytes = Mw * 8;
-            hipLaunchKernelGGL((k_commutes<true, false>), grid, dim3(256), 0, ctx().stream, at.as<u64>(), Npad, N, Bt + joff, Mpad, M - joff, Wq,
-                               (uint8_t *)nullptr, (i64)0, reinterpret_cast<uint8_t *>(bits_dst) + (joff >> 3), stride_bytes);
+        if (out_bits) {
+            hipLaunchKernelGGL((k_commutes<true, false>), grid, dim3(256), 0, ctx().stream, At, pl.Npad, N, Bt + joff, pl.Mpad, M - joff, Wq,
+                               (uint8_t *)nullptr, (i64)0, reinterpret_cast<uint8_t *>(out_bits) + (joff >> 3), stride_bytes);
         } else {
             // The output base is shifted so that column j of this launch maps to joff + j of the full row.
-            hipLaunchKernelGGL((k_commutes<false, true>), grid, dim3(256), 0, ctx().stream, at.as<u64>(), Npad, N, Bt + joff, Mpad, M - joff, Wq,
+            hipLaunchKernelGGL((k_commutes<false, true>), grid, dim3(256), 0, ctx().stream, At, pl.Npad, N, Bt + joff, pl.Mpad, M - joff, Wq,
                                out + joff, M, (uint8_t *)nullptr, (i64)0);
         }
         KERNEL_CHECK();
@@ -230,70 +152,3 @@ int commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out,
 }
 
 }  // namespace symgpu
-
-using namespace symgpu;
-
-extern "C" {
-
-int symgpu_ycount(const uint64_t *rows, int64_t T, int Wq, int64_t *out) {
-    SG_ENTER();
-    SG_REQUIRE(T >= 0 && Wq >= 1 && (T == 0 || (rows && out)), "ycount");
-    if (T == 0) return SYMGPU_OK;
-    Scratch d, o;
-    SG_TRY(d.alloc((size_t)T * 2 * Wq * sizeof(u64)));
-    SG_TRY(o.alloc((size_t)T * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(d.p, rows, (size_t)T * 2 * Wq * sizeof(u64), hipMemcpyHostToDevice, ctx().stream));
-    count_h2d((size_t)T * 2 * Wq * sizeof(u64)); count_d2h((size_t)T * sizeof(int));
-    SG_TRY(ycount_dev(d.as<u64>(), T, Wq, o.as<int>()));
-    int *h = (int *)malloc((size_t)T * sizeof(int));
-    if (!h) { set_error("host allocation failed"); return SYMGPU_E_NOMEM; }
-    hipError_t e = hipMemcpyAsync(h, o.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, ctx().stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);
-    if (e != hipSuccess) { free(h); return hip_fail(e, "ycount download", __FILE__, __LINE__); }
-    for (i64 t = 0; t < T; ++t) out[t] = h[t];
-    free(h);
-    return SYMGPU_OK;
-}
-
-int symgpu_commutes_dev(symgpu_op_t A, int64_t a_begin, int64_t a_end, symgpu_op_t B, uint8_t *out_dev) {
-    SG_ENTER(A, B);
-    SG_REQUIRE(A && B && A->Wq == B->Wq, "commutes_dev: operands must share Wq");
-    SG_REQUIRE(0 <= a_begin && a_begin <= a_end && a_end <= A->T, "commutes_dev: bad row range");
-    SG_REQUIRE(out_dev || a_end == a_begin || B->T == 0, "commutes_dev: null output");
-    return commutes_dev(A->rows + a_begin * 2 * A->Wq, a_end - a_begin, B->rows, B->T, A->Wq, out_dev, nullptr, B);
-}
-
-int symgpu_commutes_bits_dev(symgpu_op_t A, int64_t a_begin, int64_t a_end, symgpu_op_t B, uint64_t *out_bits_dev) {
-    SG_ENTER(A, B);
-    SG_REQUIRE(A && B && A->Wq == B->Wq, "commutes_bits_dev: operands must share Wq");
-    SG_REQUIRE(0 <= a_begin && a_begin <= a_end && a_end <= A->T, "commutes_bits_dev: bad row range");
-    SG_REQUIRE(out_bits_dev || a_end == a_begin || B->T == 0, "commutes_bits_dev: null output");
-    return commutes_dev(A->rows + a_begin * 2 * A->Wq, a_end - a_begin, B->rows, B->T, A->Wq, nullptr, out_bits_dev, B);
-}
-
-int symgpu_commutes(const uint64_t *A, int64_t N, const uint64_t *B, int64_t M, int Wq, uint8_t *out) {
-    SG_ENTER();
-    SG_REQUIRE(N >= 0 && M >= 0 && Wq >= 1, "commutes: sizes");
-    if (N == 0 || M == 0) return SYMGPU_OK;
-    SG_REQUIRE(A && B && out, "commutes: null pointer");
-    const size_t rb = (size_t)2 * Wq * sizeof(u64);
-    Scratch da, db, dout;
-    SG_TRY(da.alloc((size_t)N * rb));
-    HIP_TRY(hipMemcpyAsync(da.p, A, (size_t)N * rb, hipMemcpyHostToDevice, ctx().stream));
-    count_h2d((size_t)N * rb); count_d2h((size_t)N * (size_t)M);
-    const u64 *pb = da.as<u64>();
-    if (!(B == A && M == N)) {
-        SG_TRY(db.alloc((size_t)M * rb));
-        HIP_TRY(hipMemcpyAsync(db.p, B, (size_t)M * rb, hipMemcpyHostToDevice, ctx().stream));
-        count_h2d((size_t)M * rb);
-        pb = db.as<u64>();
-    }
-    SG_TRY(dout.alloc((size_t)N * (size_t)M));
-    SG_TRY(commutes_dev(da.as<u64>(), N, pb, M, Wq, dout.as<uint8_t>(), nullptr));
-    prefault_host(out, (size_t)N * (size_t)M);
-    HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)N * (size_t)M, hipMemcpyDeviceToHost, ctx().stream));
-    HIP_TRY(hipStreamSynchronize(ctx().stream));
-    return SYMGPU_OK;
-}
-
-}  // extern "C"

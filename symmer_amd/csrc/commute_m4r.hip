@@ -1,5 +1,5 @@
-// commute_m4r.hip — termwise commutation as a GF(2) matrix product by the Method of Four Russians, tables in LDS: operand preparation of
-// the right operand, kernel choice and output handling.  The kernel itself is commute_m4r7.hip.
+// commute_m4r.hip — termwise commutation as a GF(2) matrix product by the Method of Four Russians, tables in LDS: preparation of the right
+// operand and expansion of bit-packed output.  The kernel itself is commute_m4r7.hip, the choice of kernel and tile plan_commutes (commute_driver.hip).
 // (reference: symmer/operators/base.py:938-971 -> matmul_GF2 / numba_dot_matmal_GF2, utils.py:9-78: f64 dgemm, then % 2)
 //
 //   C = NOT( A . Omega . B^T  mod 2 ),  A: N x 2n bits, B: M x 2n bits       (True = commute)
@@ -14,17 +14,9 @@
 //
 //   BT[c][jw]   bit c of B rows 64jw..64jw+63 (bit-major copy, cached on the operator); row c of the contraction pairs A bit c with B bit
 //               c +- 64Wq (x with z', z with x'), which is just a row offset into BT.
-#include "common.h"
-#include <stdlib.h>
+#include "commute_common.h"
 
 namespace symgpu {
-
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) u64x2 lds_u64x2;            // raw LDS address -> ds_read_b128 without a base add
-
-constexpr int MK_TILE_W = 32;                         // 64-bit words per column tile: 2048 columns
 
 // bit-major copy of B: BT[c][jw], c = 64*sw + bit.  One wave transposes eight 64 x 64 bit blocks of one source word and
 // writes 64 contiguous bytes per bit-row.
@@ -97,13 +89,7 @@ __global__ __launch_bounds__(256) void k_bits_to_bytes_flat(const u64 *__restric
                 if (++jj == M) { jj = 0; ++ii; }
             }
         }
-        u32x4 v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const u32 x = (b16 >> (4 * q)) & 0xFu;
-            v[q] = (x | (x << 7) | (x << 14) | (x << 21)) & 0x01010101u;
-        }
-        __builtin_nontemporal_store(v, dst + c);
+        __builtin_nontemporal_store(bits16_to_bytes(b16), dst + c);
     }
 }
 
@@ -118,77 +104,24 @@ int bits_to_bytes_dev(const u64 *bits, i64 stride_words, i64 N, i64 M, uint8_t *
     return SYMGPU_OK;
 }
 
-static i64 round_up_i64(i64 x, i64 m) { return (x + m - 1) / m * m; }
-
-// tile heights: R rows per 16-lane slot -> 32 R rows per workgroup.  Taller tiles amortise the tables over more rows (round 5, 200,000^2
-// terms at n = 2000: R = 16 / 24 / 48 -> 60.0 / 50.8 / 36.1 ms), but a workgroup finishes a tile with a store phase no other work on its CU
-// hides, so a launch wants several tiles per CU for the stores of one workgroup to fall under the lookups of the others — the more, the
-// shorter the tile's lookup phase is.  Measured (round 6, profiles/r06_m4r_pick.txt, n in 20..2000 x N in 20,000..100,000): the tallest
-// height with  tiles x steps-per-tile >= 200 x CUs  is within 5 % of the best of the three everywhere; below 32 steps (n <= 192: rows of at
-// most three words a half) the table is bound by its own bytes and R = 16 is never beaten.  SYMGPU_M4R_R forces one (tests).
-static i64 m4r_workgroups(i64 N, i64 M, int R) {
-    const i64 Mw = (M + 63) / 64;
-    return ((N + 32 * R - 1) / (32 * R)) * ((Mw + MK_TILE_W - 1) / MK_TILE_W);
-}
-static int m4r_pick(i64 N, i64 M, int Wq) {
-    if (const char *e = getenv("SYMGPU_M4R_R")) {
-        const int r = atoi(e);
-        if (r == 16 || r == 24 || r == 48) return r;
+// the bit-major copy of B is cached on its operator (an adjacency matrix computed slab by slab transposes B once)
+int m4r_bit_major(const CommutePlan &pl, const u64 *B, i64 M, int W, symgpu_op_s *b_owner, Scratch &scratch, const u64 **bt) {
+    symgpu_op_s *const cache = (b_owner && b_owner->rows == B && b_owner->T == M) ? b_owner : nullptr;
+    u64 *build = nullptr;                                              // where a copy has to be built; null: the cached one is valid
+    if (!cache) {
+        SG_TRY(scratch.alloc(pl.bt_bytes));
+        build = scratch.as<u64>();
+    } else if (!cache->bt || cache->bt_T != M || cache->bt_pad != pl.Mw_pad) {
+        if (cache->bt) { dev_free(cache->bt); cache->bt = nullptr; }
+        SG_TRY(dev_alloc(pl.bt_bytes, (void **)&cache->bt));
+        build = cache->bt;
     }
-    const i64 steps = ((128 * (i64)Wq + 6) / 7 + 1) / 2;
-    if (steps < 32) return 16;
-    const int cand[2] = {48, 24};
-    for (int R : cand)
-        if (m4r_workgroups(N, M, R) * steps >= (i64)200 * ctx().num_cu) return R;
-    return 16;
-}
-// enough 512 x 2048 tiles to occupy most of the chip (below that the register-tile kernel wins: 1024 x 16384 at n = 2000 takes
-// 0.10 ms there and 0.6 ms here; 4096 x 65536: 1.03 ms against 0.66 ms)
-// — and tiles that are at least half full in both directions: a 512 x 2048 tile costs the same whether it holds 1 row or 512
-// (100,000 x 1 at n = 1000: 0.14 ms on the register-tile kernel, 0.34 ms here)
-bool commutes_m4r_worthwhile(i64 N, i64 M) { return N >= 256 && M >= 1024 && m4r_workgroups(N, M, 16) >= (3 * ctx().num_cu) / 4; }
-
-// Same contract as commutes_dev (commute.hip): exactly one of out / out_bits is non-null.
-int commutes_m4r_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner) {
-    if (N == 0 || M == 0) return SYMGPU_OK;
-    hipStream_t st = ctx().stream;
-    const int W = 2 * Wq;
-    const int R = m4r_pick(N, M, Wq);
-    const i64 Mw = (M + 63) / 64, Mw_pad = round_up_i64(Mw, MK_TILE_W);
-    Scratch bt, bits;
-    // the bit-major copy of B is cached on its operator (an adjacency matrix computed slab by slab transposes B once)
-    const u64 *bt_p = nullptr;
-    if (b_owner && b_owner->rows == B && b_owner->T == M) {
-        if (!b_owner->bt || b_owner->bt_T != M || b_owner->bt_pad != Mw_pad) {
-            if (b_owner->bt) { dev_free(b_owner->bt); b_owner->bt = nullptr; }
-            SG_TRY(dev_alloc((size_t)64 * W * Mw_pad * 8, (void **)&b_owner->bt));
-            hipLaunchKernelGGL(k_m4r_bt, dim3((unsigned)((Mw_pad / 8 + 3) / 4), (unsigned)W), dim3(256), 0, st, B, M, W, b_owner->bt, Mw_pad);
-            KERNEL_CHECK();
-            b_owner->bt_pad = Mw_pad;
-            b_owner->bt_T = M;
-        }
-        bt_p = b_owner->bt;
-    } else {
-        SG_TRY(bt.alloc((size_t)64 * W * Mw_pad * 8));
-        hipLaunchKernelGGL(k_m4r_bt, dim3((unsigned)((Mw_pad / 8 + 3) / 4), (unsigned)W), dim3(256), 0, st, B, M, W, bt.as<u64>(), Mw_pad);
+    if (build) {
+        hipLaunchKernelGGL(k_m4r_bt, dim3((unsigned)((pl.Mw_pad / 8 + 3) / 4), (unsigned)W), dim3(256), 0, ctx().stream, B, M, W, build, pl.Mw_pad);
         KERNEL_CHECK();
-        bt_p = bt.p ? bt.as<u64>() : nullptr;
+        if (cache) { cache->bt_pad = pl.Mw_pad; cache->bt_T = M; }
     }
-    // np.bool_ output: expanded by the kernel's own epilogue, rows of any length at any base (unaligned 16-byte stores where they have to be).
-    // SYMGPU_M4R_UNFUSED=1: bit-packed rows to scratch + the flat expansion kernel (a second pass: 2.8 against 2.3 ms at 100,000^2 terms of 20
-    // qubits, but 0.30 against 0.36 ms at 30,000^2) — kept as the tested alternative.
-    const bool fused_bytes = out && !getenv("SYMGPU_M4R_UNFUSED");
-    void *dst = out_bits;
-    i64 stride = Mw;
-    if (fused_bytes) {
-        dst = out;
-        stride = M;
-    } else if (out) {
-        SG_TRY(bits.alloc((size_t)N * Mw * 8));
-        dst = bits.p;
-    }
-    SG_TRY(commutes_m4r7_launch(A, N, M, Wq, bt_p, Mw_pad, R, fused_bytes, dst, stride));
-    if (out && !fused_bytes) SG_TRY(bits_to_bytes_dev(bits.as<u64>(), stride, N, M, out));
+    *bt = cache ? cache->bt : scratch.as<u64>();
     return SYMGPU_OK;
 }
 

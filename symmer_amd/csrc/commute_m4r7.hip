@@ -41,26 +41,18 @@
 //              with row c + 64Wq (c in the X half) or c - 64Wq (Z half).
 //   klist      the groups in which A has any non-zero value, ascending, padded to an even count with the zero group.
 //   steptab    per pair of groups: index offsets and BT row offsets (second half of k_m7_klist).
-#include "common.h"
+#include "commute_common.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <type_traits>
 
 namespace symgpu {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int M7_TILE_W = 32;                          // 64-bit words per column tile: 2048 columns
 constexpr int M7_ENTRY_BYTES = M7_TILE_W * 8;          // 256
-constexpr int M7_STREAM_MIN_WORK = 125;                // tile-steps per persistent workgroup from which it pays
-constexpr int M7_STREAM_MIN_STEPS = 32;                // steps a tile (pairs of 7-bit groups of the padded row: 28 at n <= 192, 37 above) from which the stream-K launch pays
 constexpr int M7_TABLE_BYTES = 128 * M7_ENTRY_BYTES;   // 32 KiB: one 7-bit group
 constexpr int M7_BUF_BYTES = 2 * M7_TABLE_BYTES;       // the two tables of a step
 constexpr int M7_LDS = 2 * M7_BUF_BYTES;               // double buffered: 128 KiB
 constexpr int M7_BT_STAGE = 14 * M7_ENTRY_BYTES;       // the 14 bit-rows of a step: 3.5 KiB
-constexpr int M7_WAVES = 8;
 
 __device__ __forceinline__ u32 xor3(u32 a, u32 b, u32 c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 
@@ -169,6 +161,12 @@ __device__ __forceinline__ void m7_store16(uint8_t *dst, u32x4 v, i64 cols_left)
     } else {
         for (int b = 0; b < (int)cols_left; ++b) dst[b] = (uint8_t)(v[b >> 2] >> (8 * (b & 3)));
     }
+}
+// one word of a bit-packed result row from the parities of its 64 pairs: commute = NOT parity; columns >= M stay zero
+__device__ __forceinline__ void m7_store_word(u64 *out_bits, i64 out_stride, i64 i, i64 jw, i64 Mw, u64 last_mask, u64 parity) {
+    u64 v = ~parity;
+    if (jw == Mw - 1) v &= last_mask;
+    out_bits[i * out_stride + jw] = v;
 }
 // a lane index the optimiser cannot see through: what is computed from it stays where it is used (the epilogues' per-lane constants would
 // otherwise be hoisted out of the job loop and held in registers through the look-up stream, which has none to spare)
@@ -483,19 +481,13 @@ __global__ __launch_bounds__(64 * M7_WAVES) void k_commutes_m4r7s(const uint8_t 
                     const i64 col = (tile_w0 << 6) + half * 1024 + lane_e * 16;
                     if (i < N && col < m_cols) {
                         const u32 b16 = *reinterpret_cast<const uint16_t *>(region + (s * RO + jj) * M7_ENTRY_BYTES + half * 128 + lane_e * 2);
-                        u32x4 v;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const u32 x = (b16 >> (4 * k)) & 0xFu;
-                            v[k] = (x | (x << 7) | (x << 14) | (x << 21)) & 0x01010101u;
-                        }
+                        const u32x4 v = bits16_to_bytes(b16);
                         m7_store16(out + i * out_stride + col, v, m_cols - col);
                     }
                 }
                 __syncthreads();
             }
         } else {
-            // commute = NOT parity; columns >= M stay zero
             u64 *const out_bits = reinterpret_cast<u64 *>(out_v);
             const i64 Mw = (m_cols + 63) >> 6;
             const u64 last_mask = (m_cols & 63) ? ((1ULL << (m_cols & 63)) - 1) : ~0ULL;
@@ -507,11 +499,7 @@ __global__ __launch_bounds__(64 * M7_WAVES) void k_commutes_m4r7s(const uint8_t 
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const i64 jw = tile_w0 + 2 * wp_e + h;
-                        if (jw < Mw) {
-                            u64 v = ~(h ? ((u64)acc[j].w << 32) | acc[j].z : ((u64)acc[j].y << 32) | acc[j].x);
-                            if (jw == Mw - 1) v &= last_mask;
-                            out_bits[i * out_stride + jw] = v;
-                        }
+                        if (jw < Mw) m7_store_word(out_bits, out_stride, i, jw, Mw, last_mask, h ? ((u64)acc[j].w << 32) | acc[j].z : ((u64)acc[j].y << 32) | acc[j].x);
                     }
                 }
             }
@@ -543,12 +531,7 @@ __global__ __launch_bounds__(256) void k_m7_fixup(const u64 *__restrict__ part, 
             if (i >= N || col >= m_cols) continue;
             const u64 w = ~(pt[lr * M7_TILE_W + (c >> 2)] ^ ph[lr * M7_TILE_W + (c >> 2)]);
             const u32 b16 = (u32)(w >> (16 * (c & 3))) & 0xFFFFu;
-            u32x4 v;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u32 x = (b16 >> (4 * k)) & 0xFu;
-                v[k] = (x | (x << 7) | (x << 14) | (x << 21)) & 0x01010101u;
-            }
+            const u32x4 v = bits16_to_bytes(b16);
             m7_store16(out + i * out_stride + col, v, m_cols - col);
         }
     } else {
@@ -559,46 +542,53 @@ __global__ __launch_bounds__(256) void k_m7_fixup(const u64 *__restrict__ part, 
             const int lr = idx / M7_TILE_W, wd = idx % M7_TILE_W;
             const i64 i = rt * WG_ROWS + lr, jw = ct * M7_TILE_W + wd;
             if (i >= N || jw >= Mw) continue;
-            u64 v = ~(pt[idx] ^ ph[idx]);
-            if (jw == Mw - 1) v &= last_mask;
-            out_bits[i * out_stride + jw] = v;
+            m7_store_word(out_bits, out_stride, i, jw, Mw, last_mask, pt[idx] ^ ph[idx]);
         }
     }
 }
 
+// the arguments every instantiation of the kernel takes
+struct M7Launch {
+    const uint8_t *A7;
+    i64 N;
+    const u64 *BT, *steptab;
+    const u32 *np;                                                    // device: the steps of a tile (k_m7_klist)
+    void *out;
+    i64 stride, M;
+    u32 *flags;                                                       // the context's flag words and this launch's epoch (m7_next_epoch)
+    u32 epoch;
+};
+
+// [P] "head part published" + [P] "tile left to the fix-up launch" of a stream-K launch, compared with the launch's epoch: the words are
+// allocated with the context's first Four-Russians launch, every launch takes the next epoch (never 0: the words start as zeros)
+static int m7_next_epoch(int num_cu, u32 **flags, u32 *epoch) {
+    constexpr int MAX_CU = 1024;
+    SG_REQUIRE(num_cu <= MAX_CU, "commutes_m4r7: more than 1024 compute units");
+    Context &c = ctx();
+    if (!c.m7_flags) {
+        HIP_TRY(hipMalloc((void **)&c.m7_flags, (size_t)2 * MAX_CU * 4));
+        HIP_TRY(hipMemsetAsync(c.m7_flags, 0, (size_t)2 * MAX_CU * 4, c.stream));
+    }
+    if (++c.m7_epoch == 0) c.m7_epoch = 1;
+    *flags = c.m7_flags;
+    *epoch = c.m7_epoch;
+    return SYMGPU_OK;
+}
+
 template <int R, int LOOKP, int CH, int NS>
-static int launch_m7s(const uint8_t *A7, i64 Npad, i64 N, const u64 *BT, i64 Mw_pad, const u64 *steptab, const u32 *np, void *out, i64 stride, i64 M, bool bytes, int max_steps) {
+static int launch_m7s(const CommutePlan &pl, const M7Launch &a) {
     const bool attr = SG_DEVICE_ONCE(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_commutes_m4r7s<R, LOOKP, CH, NS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          M7S_LDS) == hipSuccess);
     if (!attr) { set_error("commutes_m4r7: %d bytes of LDS refused", M7S_LDS); return SYMGPU_E_HIP; }
-    constexpr i64 WG_ROWS = 4 * M7_WAVES * R;
-    const i64 n_rt = Npad / WG_ROWS, n_ct = Mw_pad / M7_TILE_W, n_tiles = n_rt * n_ct;
-    const int P = ctx().num_cu;
-    // one tile per workgroup where the persistent launch's published parts only cost: short operators (below M7_STREAM_MIN_STEPS steps a
-    // tile the table is bound by its own bytes — 30,000^2 terms of 20 / 100 / 150 qubits, R = 16: 0.339 / 0.370 / 0.372 ms streamed against
-    // 0.284 / 0.307 / 0.339 ms tile by tile), launches of little work (20,000^2 terms of 200 / 300 / 400 qubits: 0.220 / 0.238 / 0.259 against
-    // 0.189 / 0.219 / 0.254 ms; the streamed launch wins from about 125 tile-steps per workgroup) and fewer tiles than compute units
-    // (profiles/r06_m4r_pick.txt).  Runtime switches ("Environment switches"): both force a path the kernel takes by itself.
-    bool stream = n_tiles >= P && max_steps >= M7_STREAM_MIN_STEPS && n_tiles * max_steps >= (i64)M7_STREAM_MIN_WORK * P;
-    if (const char *e = getenv("SYMGPU_M4R_STREAM")) stream = n_tiles >= P && atoi(e) != 0;
-    const int force_fixup = getenv("SYMGPU_M4R_FIXUP") ? 1 : 0;
-    bump_counter(stream ? 21 : 20);                                   // which launch this is (symgpu_debug_counter 20 / 21)
+    const int P = pl.num_cu, bytes = pl.fused_bytes ? 1 : 0;
     Scratch part, dbgbuf;
-    Context &c = ctx();
-    if (!c.m7_flags) {                                                // [P] "head part published" + [P] "tile left to the fix-up launch", compared with the launch's epoch
-        HIP_TRY(hipMalloc((void **)&c.m7_flags, (size_t)2 * 1024 * 4));
-        HIP_TRY(hipMemsetAsync(c.m7_flags, 0, (size_t)2 * 1024 * 4, c.stream));
-    }
-    if (++c.m7_epoch == 0) c.m7_epoch = 1;
-    SG_REQUIRE(P <= 1024, "commutes_m4r7: more than 1024 compute units");
-    if (stream) SG_TRY(part.alloc((size_t)P * 2 * WG_ROWS * M7_TILE_W * 8));
+    if (pl.stream) SG_TRY(part.alloc(pl.part_bytes));
     u64 *dbg = nullptr;
 #ifdef SYMGPU_M7_STAMPS
     if (getenv("SYMGPU_M4R_STAMPS")) { SG_TRY(dbgbuf.alloc(64 * 8)); HIP_TRY(hipMemsetAsync(dbgbuf.p, 0, 64 * 8, ctx().stream)); dbg = dbgbuf.as<u64>(); }
 #endif
-    SG_REQUIRE(n_tiles < (i64)1 << 31, "commutes_m4r7: tile count");
-    hipLaunchKernelGGL((k_commutes_m4r7s<R, LOOKP, CH, NS>), dim3((unsigned)(stream ? P : n_tiles)), dim3(64 * M7_WAVES), M7S_LDS, ctx().stream, A7, Npad, N, BT, Mw_pad,
-                       steptab, np, out, stride, M, bytes ? 1 : 0, part.as<u64>(), n_rt, n_tiles, stream ? 1 : 0, force_fixup, dbg, c.m7_flags, c.m7_epoch);
+    hipLaunchKernelGGL((k_commutes_m4r7s<R, LOOKP, CH, NS>), dim3((unsigned)(pl.stream ? P : pl.n_tiles)), dim3(64 * M7_WAVES), M7S_LDS, ctx().stream, a.A7, pl.Npad, a.N, a.BT,
+                       pl.Mw_pad, a.steptab, a.np, a.out, a.stride, a.M, bytes, part.as<u64>(), pl.n_rt, pl.n_tiles, pl.stream ? 1 : 0, pl.force_fixup ? 1 : 0, dbg, a.flags, a.epoch);
     KERNEL_CHECK();
 #ifdef SYMGPU_M7_STAMPS
     if (dbg) {
@@ -611,39 +601,50 @@ static int launch_m7s(const uint8_t *A7, i64 Npad, i64 N, const u64 *BT, i64 Mw_
                     (double)h[w * 8 + 3] / (double)(h[w * 8 + 6] ? h[w * 8 + 6] : 1), (double)h[w * 8 + 4] / (double)(h[w * 8 + 6] ? h[w * 8 + 6] : 1), (double)h[w * 8 + 5] / (double)(h[w * 8 + 6] ? h[w * 8 + 6] : 1));
     }
 #endif
-    if (stream) {
-        hipLaunchKernelGGL((k_m7_fixup<R>), dim3((unsigned)(P - 1), 24), dim3(256), 0, ctx().stream, part.as<u64>(), np, n_rt, n_tiles, P, N, out, stride, M, bytes ? 1 : 0, c.m7_flags, c.m7_epoch);
+    if (pl.stream) {
+        hipLaunchKernelGGL((k_m7_fixup<R>), dim3((unsigned)(P - 1), 24), dim3(256), 0, ctx().stream, part.as<u64>(), a.np, pl.n_rt, pl.n_tiles, P, a.N, a.out, a.stride, a.M, bytes, a.flags, a.epoch);
         KERNEL_CHECK();
     }
     return SYMGPU_OK;
 }
 
-// prepared operands of one call (A7, flags, klist) and the launch; bt_p = bit-major copy of B (built / cached by commutes_m4r_dev)
-int commutes_m4r7_launch(const u64 *A, i64 N, i64 M, int Wq, const u64 *bt_p, i64 Mw_pad, int R, bool bytes, void *dst, i64 stride) {
+// the prepared left operand of one call (A7, flags, klist, step table) and the launch the plan names; bt = bit-major copy of B (m4r_bit_major)
+int launch_four_russians(const CommutePlan &pl, const u64 *A, i64 N, i64 M, int Wq, const u64 *bt, void *dst, i64 stride) {
     hipStream_t st = ctx().stream;
-    const int W = 2 * Wq, ng7 = (128 * Wq + 6) / 7;
-    const i64 Npad = (N + (i64)4 * M7_WAVES * R - 1) / ((i64)4 * M7_WAVES * R) * ((i64)4 * M7_WAVES * R);   // multiples of 256
+    const int W = 2 * Wq;
+    SG_REQUIRE(pl.n_tiles < (i64)1 << 31, "commutes_m4r7: tile count");
     Scratch a7, flags, klist;
-    SG_TRY(a7.alloc((size_t)(ng7 + 1) * Npad));
-    const size_t flag_bytes = ((size_t)(ng7 + 1) * 4 + 255) / 256 * 256;   // (a whole number of 256-byte pieces: one fill kernel, not a body and a tail)
-    SG_TRY(flags.alloc(flag_bytes));
-    SG_TRY(klist.alloc((size_t)(ng7 + 2) * 4));
-    HIP_TRY(hipMemsetAsync(flags.p, 0, flag_bytes, st));
-    hipLaunchKernelGGL(k_m7_a7, dim3((unsigned)(Npad / 256), (unsigned)((W + A7_CW - 1) / A7_CW)), dim3(256), 0, st, A, N, W, ng7, a7.as<uint8_t>(), Npad, flags.as<u32>());
+    SG_TRY(a7.alloc(pl.a7_bytes));
+    SG_TRY(flags.alloc(pl.flag_bytes));
+    SG_TRY(klist.alloc(pl.klist_bytes));
+    HIP_TRY(hipMemsetAsync(flags.p, 0, pl.flag_bytes, st));
+    hipLaunchKernelGGL(k_m7_a7, dim3((unsigned)(pl.Npad / 256), (unsigned)((W + A7_CW - 1) / A7_CW)), dim3(256), 0, st, A, N, W, pl.ng7, a7.as<uint8_t>(), pl.Npad, flags.as<u32>());
     KERNEL_CHECK();
-    u32 *np = flags.as<u32>() + ng7;
+    u32 *np = flags.as<u32>() + pl.ng7;
     Scratch steptab;
-    const int max_pairs = (ng7 + 1) / 2;
-    SG_TRY(steptab.alloc((size_t)(max_pairs + 2) * 16 * 8));
-    hipLaunchKernelGGL(k_m7_klist, dim3(1), dim3(64), 0, st, flags.as<u32>(), ng7, klist.as<u32>(), np, max_pairs, Npad, Mw_pad, Wq, steptab.as<u64>());
+    SG_TRY(steptab.alloc(pl.steptab_bytes));
+    hipLaunchKernelGGL(k_m7_klist, dim3(1), dim3(64), 0, st, flags.as<u32>(), pl.ng7, klist.as<u32>(), np, pl.max_pairs, pl.Npad, pl.Mw_pad, Wq, steptab.as<u64>());
     KERNEL_CHECK();
     ProfScope prof(1);
-#define M7S_ARGS a7.as<uint8_t>(), Npad, N, bt_p, Mw_pad, steptab.as<u64>(), np, dst, stride, M, bytes, max_pairs
-    if (R == 48) SG_TRY((launch_m7s<48, 3, 8, 3>(M7S_ARGS)));
-    else if (R == 24) SG_TRY((launch_m7s<24, 4, 8, 3>(M7S_ARGS)));
-    else SG_TRY((launch_m7s<16, 4, 4, 4>(M7S_ARGS)));
-#undef M7S_ARGS
-    return SYMGPU_OK;
+    u32 *epoch_flags = nullptr;
+    u32 epoch = 0;
+    SG_TRY(m7_next_epoch(pl.num_cu, &epoch_flags, &epoch));
+    M7Launch a;
+    a.A7 = a7.as<uint8_t>();
+    a.N = N;
+    a.BT = bt;
+    a.steptab = steptab.as<u64>();
+    a.np = np;
+    a.out = dst;
+    a.stride = stride;
+    a.M = M;
+    a.flags = epoch_flags;
+    a.epoch = epoch;
+    switch (pl.R) {
+        case 48: return launch_m7s<48, 3, 8, 3>(pl, a);
+        case 24: return launch_m7s<24, 4, 8, 3>(pl, a);
+        default: return launch_m7s<16, 4, 4, 4>(pl, a);
+    }
 }
 
 }  // namespace symgpu

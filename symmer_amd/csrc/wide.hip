@@ -112,7 +112,7 @@ static int wide_counts(const u64 *inner, i64 Ni, const u64 *outer, i64 No, int W
     return SYMGPU_OK;
 }
 
-// commutes_dev's contract (commute.hip): exactly one of out / out_bits is non-null
+// commutes_dev's contract (commute_driver.hip): exactly one of out / out_bits is non-null
 int wide_commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits) {
     Scratch acc;
     SG_TRY(acc.alloc((size_t)N * M * 2 * sizeof(u32)));

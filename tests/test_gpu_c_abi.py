@@ -649,9 +649,10 @@ def refusal_cases():
         ('rotate_clifford_chain_dev/not-clean', 'rotate_clifford_chain_dev', lambda L, o: L.symgpu_rotate_clifford_chain_dev(o.a, R(o), ptr(keep_ok), I64(2), byref(out))),
         ('rotate_clifford_chain_dev/null-ks', 'rotate_clifford_chain_dev', lambda L, o: L.symgpu_rotate_clifford_chain_dev(o.a, R(o), None, I64(2), byref(out))),
         ('perform_rotations_dev/null-out', 'perform_rotations_dev', lambda L, o: L.symgpu_perform_rotations_dev(o.a, R(o), B, B, ptr(keep_ok), I64(1), DBL(1e-15), 0, None, None, byref(n64), byref(i32))),
-        # commute.hip
+        # ycount.hip
         ('ycount/Wq-0', 'ycount', lambda L, o: L.symgpu_ycount(R(o), I64(12), 0, B)),
         ('ycount/null-out', 'ycount', lambda L, o: L.symgpu_ycount(R(o), I64(12), 2, None)),
+        # commute_driver.hip
         ('commutes/Wq-0', 'commutes', lambda L, o: L.symgpu_commutes(R(o), I64(12), R(o), I64(12), 0, B)),
         ('commutes/negative-M', 'commutes', lambda L, o: L.symgpu_commutes(R(o), I64(12), R(o), I64(-1), 2, B)),
         ('commutes/null-out', 'commutes', lambda L, o: L.symgpu_commutes(R(o), I64(12), R(o), I64(12), 2, None)),

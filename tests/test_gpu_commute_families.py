@@ -1,4 +1,5 @@
-"""GPU: every commutation kernel (csrc/commute.hip, commute_m4r.hip, commute_m4r7.hip, the wide-row path of wide.hip) on operands whose
+"""GPU: every commutation kernel (csrc/commute.hip, commute_m4r.hip, commute_m4r7.hip, the wide-row path of wide.hip; the path of a call is
+planned in commute_driver.hip) on operands whose
 tables hold BY CONSTRUCTION (tests/_commute_families.py; tests/test_commute_families.py proves the answers against the NumPy oracle on the
 CPU), bit for bit, with the path each call took asserted through symgpu_debug_counter 18-21:
 
@@ -20,6 +21,7 @@ import pytest
 
 from symmer_amd import kernels, packing, _lib, PauliwordOp
 from symmer_amd.kernels import DeviceOp
+from oracle import oracle_np as onp
 import _commute_families as fam
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +43,7 @@ def set_switches(monkeypatch, env):
     for k in ENV_NAMES:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
-        monkeypatch.setenv(k, v)                                      # read per call by commutes_dev / launch_m7s
+        monkeypatch.setenv(k, v)                                      # read per call (commute_driver.hip read_commute_switches; SYMGPU_WIDE: wide.hip)
 
 
 def counters():
@@ -375,7 +377,7 @@ def test_own_choice_small_table_takes_the_register_tile(monkeypatch):
 
 
 def test_own_choice_many_tiles_take_four_russians(monkeypatch):
-    """No switch set: 514 one-hot rows (n = 257) x 212,992 rows = 2 x 104 tiles of the shortest height, which commutes_m4r_worthwhile accepts
+    """No switch set: 514 one-hot rows (n = 257) x 212,992 rows = 2 x 104 tiles of the shortest height, which the plan's Four-Russians threshold accepts
     (at least 3/4 of the 256 compute units): a Four-Russians launch, either kind.  Bit-packed (13.7 MB)."""
     n, M = 257, 104 * 2048
     rng = np.random.default_rng(4)
@@ -467,3 +469,82 @@ def test_cached_bit_major_copy_follows_the_rows(monkeypatch):
         assert np.array_equal(B.download(with_coeff=False), eye[cols]), 'the operand itself'
     finally:
         A.free(); B.free(); src.free()
+
+
+# ---------------------------------------------------------------- 7. the plan: precedence of the switches, read on every call --------------
+def test_forcing_four_russians_beats_the_wide_kernel(monkeypatch):
+    """2 x 2 pairs of rows of 256 words a half (n = 16,384) take the wide-row kernel by themselves; SYMGPU_COMMUTE_M4R=1 comes first in the
+    plan: a Four-Russians launch (counter 20) and no wide-row call (counter 19)."""
+    n = 16384
+    cols = np.array([64, n + 16383])
+    A_, B_, _ = fam.one_hot(n, 2, np.random.default_rng(70), cols=cols)
+    a, b = packing.pack_rows(A_), packing.pack_rows(B_)
+    assert a.shape == (2, 512) and b.shape == (2, 512)
+    want = fam.pack_cols(onp.commutes_termwise(A_, B_))
+    A, B = DeviceOp.upload(a), DeviceOp.upload(b)
+    try:
+        set_switches(monkeypatch, {})
+        both_outputs(A, B, want, WIDE, '2 x 2 at n = 16384, no switch', where_left(n, cols))
+        set_switches(monkeypatch, {'SYMGPU_COMMUTE_M4R': '1'})
+        both_outputs(A, B, want, M4R_ONE, '2 x 2 at n = 16384, SYMGPU_COMMUTE_M4R=1', where_left(n, cols))
+    finally:
+        A.free(); B.free()
+
+
+PLAN_N, PLAN_M = 256, 1024                          # one tile of the shortest height at n = 100: fewer tiles than compute units
+
+
+def plan_case():
+    def build():
+        n = 100
+        A_, B_, _ = fam.sparse_groups(n, fam.group_sets(n)['five'], PLAN_N, PLAN_M, np.random.default_rng(71))
+        return packing.pack_rows(A_), packing.pack_rows(B_), onp.commutes_termwise(A_, B_)
+    return cached(('plan', PLAN_N, PLAN_M), build)
+
+
+def test_stream_asked_for_but_not_possible(monkeypatch):
+    """SYMGPU_M4R_STREAM=1 on 256 x 1024 terms at n = 100: one tile, fewer than compute units, so the launch is one tile per workgroup
+    (counter 20, not 21) and the table is the oracle's."""
+    a, b, C = plan_case()
+    set_switches(monkeypatch, {'SYMGPU_COMMUTE_M4R': '1', 'SYMGPU_M4R_STREAM': '1'})
+    A, B = DeviceOp.upload(a), DeviceOp.upload(b)
+    try:
+        both_outputs(A, B, fam.pack_cols(C), M4R_ONE, '256 x 1024 at n = 100, stream-K asked for', where_sparse)
+    finally:
+        A.free(); B.free()
+
+
+@pytest.mark.parametrize('M', [PLAN_M, PLAN_M - 24])
+def test_bit_output_ignores_unfused(M, monkeypatch):
+    """symgpu_commutes_bits_dev with and without SYMGPU_M4R_UNFUSED (which concerns byte output only): the same bits, the oracle's, zero
+    padding up to the word end (M = 1000: 24 padding bits in the last word of every row)."""
+    a, b, C = plan_case()
+    want = fam.pack_cols(C[:, :M])
+    A, B = DeviceOp.upload(a), DeviceOp.upload(np.ascontiguousarray(b[:M]))
+    try:
+        got = []
+        for env in ({'SYMGPU_COMMUTE_M4R': '1'}, {'SYMGPU_COMMUTE_M4R': '1', 'SYMGPU_M4R_UNFUSED': '1'}):
+            set_switches(monkeypatch, env)
+            what = f'256 x {M} at n = 100, bit-packed, {env}'
+            got.append(counted(lambda: table_bits(A, B), M4R_ONE, what))
+            assert_bits(got[-1], want, what, where_sparse)
+        assert np.array_equal(got[0], got[1])
+    finally:
+        A.free(); B.free()
+
+
+def test_switches_are_read_on_every_call(monkeypatch):
+    """One process, one pair of operators, four calls: SYMGPU_COMMUTE_M4R=0, =1 at SYMGPU_M4R_R=16, =1 at R=48, unset.  The register tile,
+    Four Russians twice and then the library's own choice (256 x 1024: one tile, the register tile again) serve them in that order, and
+    every table is the oracle's."""
+    a, b, C = plan_case()
+    want = fam.pack_cols(C)
+    A, B = DeviceOp.upload(a), DeviceOp.upload(b)
+    try:
+        for env, path in (({'SYMGPU_COMMUTE_M4R': '0'}, TILE), ({'SYMGPU_COMMUTE_M4R': '1', 'SYMGPU_M4R_R': '16'}, M4R_ONE),
+                          ({'SYMGPU_COMMUTE_M4R': '1', 'SYMGPU_M4R_R': '48'}, M4R_ONE), ({}, TILE)):
+            set_switches(monkeypatch, env)
+            what = f'256 x 1024 at n = 100, {env or "no switch"}'
+            assert_bytes(counted(lambda: table_bytes(A, B), path, what), want, what, where_sparse)
+    finally:
+        A.free(); B.free()

@@ -1,6 +1,6 @@
 # ad-hoc timing (not a test): the Four-Russians commutation kernel's tile height (R = 16 / 24 / 48 rows per 16-lane slot) and launch
 # (s = stream-K persistent workgroups, o = one tile per workgroup) over operator length n and term count N, next to what the library
-# picks by itself (`default`, csrc/commute_m4r.hip m4r_pick + commute_m4r7.hip launch_m7s) and the register-tile kernel (commute.hip).
+# picks by itself (`default`, csrc/commute_driver.hip plan_commutes) and the register-tile kernel (commute.hip).
 # N x N np.bool_ table, operands resident, milliseconds per call.
 #     python tools/bench_m4r_pick.py [n ...]  > profiles/rNN_m4r_pick.txt
 import sys, os, time, ctypes
