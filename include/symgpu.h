@@ -92,7 +92,13 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * what is built on them) served by the register-tile kernel / by the wide-row kernel; 20 / 21: launches of the Four-Russians commutation
  * kernel with one tile per workgroup / as stream-K (persistent workgroups over the (tile, step) space; a stream-K request with fewer tiles
  * than compute units counts as 20).  A call with no rows on either side counts nothing.  tests/test_gpu_commute_families.py asserts
- * through them which kernel a call took. */
+ * through them which kernel a call took.  22 .. 26: runs of Clifford rotations (symgpu_rotate_clifford_chain_dev with at least one row and
+ * one rotation, and the runs that symgpu_perform_rotations_dev hands to it) served by the register chain / the LDS-resident kernel / the
+ * single-workgroup kernel / the two-launch form / the four-launch form; 27 / 28: segments (of up to 40 rotations) of the register chain whose
+ * keys were sorted by the one-launch sort / by the multi-launch sort (a run that is redone after a time-out of the one-launch sort counts
+ * both).  29 / 30 / 31: single rotations (symgpu_rotate_single_dev) completed by the hash join / by the Clifford fast path / by the general
+ * path (stack + cleanup); 32: of 31, odd-k Clifford rotations whose duplicate check found two equal rows.  Rotations completed by the
+ * one-launch kernel are counted by 1 alone.  tests/test_gpu_rotation_families.py asserts through 22-32 which form and stage ran. */
 int symgpu_debug_counter(int which, int64_t *value);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so

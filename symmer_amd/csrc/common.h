@@ -125,13 +125,18 @@ void forget_bound_device();                // after a library (RCCL) may have ch
         if (!(_done.fetch_or(_bit) & _bit) && (expr)) _ok.fetch_or(_bit);                             \
         return (_ok.load() & _bit) != 0;                                                              \
     }())
-extern std::atomic<i64> g_counters[22];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
+extern std::atomic<i64> g_counters[33];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
                                            // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls),
                                            // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
                                            // [14] uses of a context by a call that did not hold its lock, [15] blocks panelled by the blocked GF(2)
                                            // elimination, [16] / [17] of these: on the full rows in LDS / on the two-word window (gf2.hip),
                                            // [18] / [19] commutation calls served by the register-tile / the wide-row kernel, [20] / [21] Four-Russians
-                                           // commutation launches with one tile per workgroup / stream-K (commute_driver.hip, one place each)
+                                           // commutation launches with one tile per workgroup / stream-K (commute_driver.hip, one place each),
+                                           // [22] .. [26] runs of Clifford rotations served by the register chain / the LDS-resident kernel / the
+                                           // single-workgroup kernel / the two-launch / the four-launch form (rotate_driver.hip run_chain, nowhere
+                                           // else), [27] / [28] segments of the register chain whose keys went to the one-launch / the multi-launch
+                                           // sort (rotate_chain.hip), [29] / [30] / [31] single rotations completed by the hash join / the Clifford
+                                           // fast path / the general path, [32] of [31]: sent there by the duplicate check (symgpu_rotate_single_dev)
 inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
 inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
 inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }

@@ -235,6 +235,7 @@ static int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u
         const int end_bit = CHAIN_IDX_BITS + 8 * ((n + 7) / 8);
         SG_TRY(radix_sort_keys_u64_coop(knew, ktmp, T, CHAIN_IDX_BITS, end_bit, &in_tmp, &coop));     // one launch for all passes up to 2^19 keys
         if (!coop) SG_TRY(radix_sort_keys_u64(knew, ktmp, T, CHAIN_IDX_BITS, end_bit, &in_tmp));
+        bump_counter(coop ? 27 : 28);                                               // (a run that is redone after a time-out counts both)
         perm = in_tmp ? ktmp : knew;
         symgpu_op_t t2 = cur; cur = other; other = t2;
     }

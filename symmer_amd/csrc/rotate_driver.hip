@@ -92,7 +92,9 @@ static ChainForm plan_chain(i64 T, int Wq, const RotateSwitches &sw) {
     return ChainForm::FourLaunch;
 }
 
+// which form served the run: symgpu_debug_counter 22 (registers) / 23 (LDS) / 24 (single workgroup) / 25 (two launches) / 26 (four launches)
 static int run_chain(ChainForm form, const ChainRun &c, int *in_b) {
+    bump_counter(22 + (int)form);
     switch (form) {
         case ChainForm::Registers: return chain_registers(c, in_b);
         case ChainForm::Lds: return chain_lds(c, in_b);
@@ -170,14 +172,23 @@ int symgpu_rotate_single_dev(symgpu_op_t in, const uint64_t *q_row_host, double 
     // exactly one analysis launch; Q reaches the device with it (in its kernel arguments when the row has <= 64 words)
     if (pl.join) {
         SG_TRY(rotate_join(r, &done));
-        if (done) return SYMGPU_OK;                                  // else duplicate rows: the general stage
+        if (done) { bump_counter(29); return SYMGPU_OK; }            // else duplicate rows: the general stage
     } else if (pl.dup_check) {
         SG_TRY(rotate_dup_check(r));
     } else {
         SG_TRY(analyze_rows(in, r.q.as<u64>(), r.anti.as<u32>(), r.ph.as<uint8_t>(), nullptr, sw, q_row_host));
     }
-    if (pl.clifford_fast && !r.has_dup) return rotate_clifford_fast(r);
-    return rotate_general(r);
+    // the stage that completed the rotation: symgpu_debug_counter 29 (hash join, above) / 30 (Clifford fast path) / 31 (general path), 32: of
+    // 31, the rotations whose duplicate check found two equal rows (the one-launch kernel counts its own: 1)
+    if (pl.clifford_fast && !r.has_dup) {
+        SG_TRY(rotate_clifford_fast(r));
+        bump_counter(30);
+        return SYMGPU_OK;
+    }
+    SG_TRY(rotate_general(r));
+    bump_counter(31);
+    if (pl.dup_check && r.has_dup) bump_counter(32);
+    return SYMGPU_OK;
 }
 
 int symgpu_perform_rotations_dev(symgpu_op_t in, const uint64_t *q_rows_host, const double *cos_t, const double *sin_t, const int *ks_host, int64_t K,

@@ -11,6 +11,7 @@ from symmer_amd import _lib, kernels, packing
 from symmer_amd.kernels import DeviceOp
 from oracle import oracle_np as onp
 from _golden import assert_op_equal
+import _rotation_families as fam
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
@@ -173,10 +174,29 @@ def test_register_chain_equals_multilaunch_chain_and_oracle(n, T, K, monkeypatch
         h.free()
 
 
-@pytest.mark.parametrize('n,T,K', [(1000, 90, 30), (1000, 128, 25), (100, 3000, 20), (64, 9000, 9), (1000, 300000 // 1000 * 10, 12)])
+# the four settings of the two switches of the library as shipped (the others are tuning knobs, compiled out), and the form each gives
+CHAIN_SETTINGS = [{}, {'SYMGPU_CHAIN_REG': '0'}, {'SYMGPU_CHAIN_REG': '0', 'SYMGPU_CHAIN_LOCAL_T': '0'}, {'SYMGPU_CHAIN_REG': '0', 'SYMGPU_CHAIN_LOCAL_T': '8192'}]
+CHAIN_FORM_CASES = [(1000, 90, 30), (1000, 128, 25), (100, 3000, 20), (64, 9000, 9), (1000, 300000 // 1000 * 10, 12), (130, 3000, 9), (130, 100, 9)]
+
+
+def chain_forms_of(n, T):
+    """The form of every setting for rows of n qubits: plan_chain restated (tests/_rotation_families.py) on the header's constants."""
+    csrc = os.path.join(os.path.dirname(HERE), 'symmer_amd', 'csrc')
+    consts = fam.header_constants(open(os.path.join(csrc, 'rotate_common.h')).read() + open(os.path.join(csrc, 'rotate_chain.hip')).read())
+    out = []
+    for env in CHAIN_SETTINGS:
+        lt = env.get('SYMGPU_CHAIN_LOCAL_T')
+        out.append(fam.FORMS.index(fam.plan_chain(T, fam.wq_of(n), consts, chain_reg='SYMGPU_CHAIN_REG' not in env, local_t=None if lt is None else int(lt))))
+    return out
+
+
+@pytest.mark.parametrize('n,T,K', CHAIN_FORM_CASES)
 def test_every_chain_form_gives_the_same_run_in_one_process(n, T, K, monkeypatch):
     """The path-selection switches are read on every call: the LDS-resident single-workgroup kernel, the L2-resident
-    one, the two-launch and the four-launch forms and the register chain must all return the same rows, order and coefficients."""
+    one, the two-launch and the four-launch forms and the register chain must all return the same rows, order and coefficients.
+    Which form served a call is read from symgpu_debug_counter 22 .. 26; the cases together reach all five (rows of 130 qubits are 3
+    chunks wide: no power of two, so they take the four-launch form where the others take the register chain or the two-launch form)."""
+    assert {f for case in CHAIN_FORM_CASES for f in chain_forms_of(*case[:2])} == set(range(5))
     rng = np.random.default_rng(31000 + n + T)
     symp, c = onp.cleanup_op(rng.random((T, 2 * n)) < 0.3, dyadic(rng, T))
     up = DeviceOp.upload(packing.pack_rows(symp), c)
@@ -184,12 +204,14 @@ def test_every_chain_form_gives_the_same_run_in_one_process(n, T, K, monkeypatch
     up.free()
     qs = packing.pack_rows(rng.random((K, 2 * n)) < 0.3)
     ks = rng.integers(0, 4, K).astype(np.int32)
-    forms = [{}, {'SYMGPU_CHAIN_REG': '0'}, {'SYMGPU_CHAIN_REG': '0', 'SYMGPU_CHAIN_LOCAL_T': '0'}, {'SYMGPU_CHAIN_LOCAL_T': '0'}]
     results = []
-    for env in forms:
+    for env, form in zip(CHAIN_SETTINGS, chain_forms_of(n, T)):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
+        before = [counter(22 + i) for i in range(5)]
         out = kernels.rotate_clifford_chain_dev(dev, qs, ks)
+        served = [counter(22 + i) - before[i] for i in range(5)]
+        assert served == [int(i == form) for i in range(5)], f'{env}: expected one call by {fam.FORMS[form]}, counters 22 .. 26 rose by {served}'
         results.append(out.download())
         out.free()
         for k in env:
