@@ -98,7 +98,9 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * keys were sorted by the one-launch sort / by the multi-launch sort (a run that is redone after a time-out of the one-launch sort counts
  * both).  29 / 30 / 31: single rotations (symgpu_rotate_single_dev) completed by the hash join / by the Clifford fast path / by the general
  * path (stack + cleanup); 32: of 31, odd-k Clifford rotations whose duplicate check found two equal rows.  Rotations completed by the
- * one-launch kernel are counted by 1 alone.  tests/test_gpu_rotation_families.py asserts through 22-32 which form and stage ran. */
+ * one-launch kernel are counted by 1 alone.  tests/test_gpu_rotation_families.py asserts through 22-32 which form and stage ran.
+ * 33 / 34 / 35: one-launch rotations LAUNCHED (completed or not) with each block's rows in LDS / in LDS and registers / left in memory;
+ * tests/test_gpu_rotate_resident.py and the full-size tests assert through them which form a shape took. */
 int symgpu_debug_counter(int which, int64_t *value);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so

@@ -11,8 +11,6 @@
 
 namespace symgpu {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // PACKED pair keys (written by product.hip's k_mul_coeff<.., KEYS>): one u64 per pair
 //     [hash: 64-F bits][e: 2 bits][o: bo bits][i: bi bits],   F = bi + bo + 2,  bi/bo = bits of Ni-1 / No-1  (bi + bo <= 32)
 // The radix sort then moves 8 instead of 12 bytes per element and pass, nothing on the path divides by Ni, the 16-byte pair

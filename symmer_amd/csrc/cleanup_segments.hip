@@ -103,7 +103,6 @@ __global__ __launch_bounds__(256) void k_zero_partial(const u64 *__restrict__ ke
 // staged in LDS, lane 0 adds them in order (two independent chains, re and im).  ~12 cycles per term: 50 us at N = 10,000 — on the
 // side stream next to the key generation and the sort of the same call, which take milliseconds.
 __global__ __launch_bounds__(64) void k_diag_seq_sum(const double *__restrict__ cf, u32 N, double *__restrict__ out) {
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
     __shared__ f64x2 s_p[2][64];
     const int lane = threadIdx.x;
     double re = 0.0, im = 0.0;

@@ -12,6 +12,8 @@
 typedef uint64_t u64;
 typedef int64_t i64;
 typedef uint32_t u32;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace symgpu {
 
@@ -64,6 +66,21 @@ struct ContextLock {
     ContextLock(const ContextLock &) {}
     ContextLock &operator=(const ContextLock &) { return *this; }
 };
+// What the one-launch rotation (rotate_resident.hip) keeps on a device between calls.
+struct ResidentState {
+    u64 *table = nullptr;          // join table [canonical-key tag 32 | row + 1 : 32], all-zero between launches (the kernel zeroes what it used)
+    size_t table_cap = 0;          // entries (power of two)
+    u32 *partner = nullptr;        // partner notes: row + 1 of the row that found this one in the table, zero between launches
+    size_t partner_cap = 0;
+    bool dirty = false;            // a launch did not complete: table and notes must be cleared before the next one
+    u64 *state = nullptr;          // granules of the two in-launch all-gathers [tag 16 | counts 48], then {fail[0], fail[1]}, {finished, published}
+    u32 epoch = 0;                 // tags the granules (2 epoch, 2 epoch + 1) and the failure words: 1 .. 16382, 0 = state to be cleared
+    bool disabled = false;         // a barrier timed out once (workgroups not co-resident): the process keeps to the multi-launch paths
+    u32 finished_base = 0;         // arrival counter base of the next launch (the counter runs on over the launches of an epoch range)
+    u32 host_tag = 0;              // tag of the last report in pinned memory, 1 .. 65535
+    u64 *trace = nullptr;          // [RES_MAX_WG][16] phase stamps of the last traced launch (SYMGPU_RES_TRACE=1) and its workgroups
+    int trace_wgs = 0;
+};
 struct Context {
     ContextLock lock;
     bool ready = false;
@@ -88,15 +105,7 @@ struct Context {
     u32 rot_gen = 0;
     u32 *rot_flags = nullptr;      // device u32[4]: [0] = generation in which a duplicate input row was seen
     void *rot_host_cnt = nullptr, *rot_host_cnt_dev = nullptr;   // pinned host copy of a rotation's counts and its device address (rotate_analyze.hip)
-    // one-launch rotation (rotate_resident.hip): partner notes [generation 10 | row + 1 : 22] of the join (same generation as
-    // rot_table), the granules of the in-launch all-gathers + failure words, and the epoch that tags them (1 .. 16382)
-    u32 *rot_partner = nullptr;
-    size_t rot_partner_cap = 0;
-    u64 *res_table = nullptr;      // its join table [canonical-key tag 32 | row + 1 : 32], all-zero between launches
-    size_t res_table_cap = 0;
-    bool res_dirty = false;        // a launch did not complete: table and notes must be cleared before the next one
-    u64 *res_state = nullptr;
-    u32 res_epoch = 0;
+    ResidentState res;             // one-launch rotation (rotate_resident.hip)
     u32 *sort_state = nullptr;     // one-launch radix sort (sort.hip): barrier counter, time-out flag, tile histograms
     u32 sort_bar_base = 0;
     bool sort_coop_disabled = false;
@@ -105,8 +114,6 @@ struct Context {
     u32 *m7_flags = nullptr;       // stream-K commutation kernel (commute_m4r7.hip): per-workgroup words compared with the launch's epoch
     u32 m7_epoch = 0;
     u32 *sort_scan_ticket = nullptr;   // radix sort: "last workgroup finishes the scan" ticket, zero between launches
-    bool res_disabled = false;     // a barrier timed out once (workgroups not co-resident): the process keeps to the multi-launch paths
-    u32 res_finished_base = 0, res_host_tag = 0;   // one-launch rotation: arrival counter base of the next launch, tag of its report
 };
 // internal names shared by context.hip, alloc.hip, transfer.hip and op_handles.hip only: kept out of the library's dynamic symbols
 #define SG_HIDDEN __attribute__((visibility("hidden")))
@@ -125,7 +132,7 @@ void forget_bound_device();                // after a library (RCCL) may have ch
         if (!(_done.fetch_or(_bit) & _bit) && (expr)) _ok.fetch_or(_bit);                             \
         return (_ok.load() & _bit) != 0;                                                              \
     }())
-extern std::atomic<i64> g_counters[33];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
+extern std::atomic<i64> g_counters[36];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
                                            // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls),
                                            // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
                                            // [14] uses of a context by a call that did not hold its lock, [15] blocks panelled by the blocked GF(2)
@@ -136,7 +143,9 @@ extern std::atomic<i64> g_counters[33];    // debug counters (symgpu_debug_count
                                            // single-workgroup kernel / the two-launch / the four-launch form (rotate_driver.hip run_chain, nowhere
                                            // else), [27] / [28] segments of the register chain whose keys went to the one-launch / the multi-launch
                                            // sort (rotate_chain.hip), [29] / [30] / [31] single rotations completed by the hash join / the Clifford
-                                           // fast path / the general path, [32] of [31]: sent there by the duplicate check (symgpu_rotate_single_dev)
+                                           // fast path / the general path, [32] of [31]: sent there by the duplicate check (symgpu_rotate_single_dev),
+                                           // [33] / [34] / [35] one-launch rotations launched with the rows in LDS / in LDS and registers / left in
+                                           // memory (rotate_resident_kernel.hip launch_resident, nowhere else)
 inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
 inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
 inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }

@@ -9,8 +9,6 @@
 
 namespace symgpu {
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int M7_TILE_W = 32;             // Four Russians: 64-bit words per column tile, 2048 columns
 constexpr int M7_WAVES = 8;               // ... waves per workgroup; a wave holds 4 slots of R rows: 32 R rows per tile
 constexpr int RT_BLOCK_ROWS = 32;         // register tile: rows of A / columns of B per workgroup (commute.hip: CI * WAVES, 64 * DJ)

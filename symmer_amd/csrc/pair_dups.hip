@@ -34,7 +34,6 @@
 
 namespace symgpu {
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 constexpr int PD_THREADS = 1024;
 constexpr int PD_QUOTA = 16;                        // pairs per lane and product bucket: 16,384 pairs per bucket at most
 constexpr int PD_TARGET = 12288;                    // pairs per product bucket the bucket width is chosen for

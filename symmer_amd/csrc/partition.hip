@@ -14,9 +14,6 @@
 
 namespace symgpu {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 static int grid_of(i64 n, int block = 256) {
     i64 g = (n + block - 1) / block;
     if (g < 1) g = 1;

@@ -155,7 +155,6 @@ __global__ __launch_bounds__(256) void k_mul_coeff_expand(const unsigned char *_
     const int e = (int)((3u * ((u32)yi[i] + (u32)yo[o]) + (p >> (2 * (r & 3)))) & 3u);
     double re, im;
     pair_coefficient(ci[2 * i], ci[2 * i + 1], cor, coi, e, re, im);
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
     const f64x2 w = {re, im};
     __builtin_nontemporal_store(w, reinterpret_cast<f64x2 *>(out) + o * out_stride + i);
 }

@@ -8,8 +8,6 @@
 
 namespace symgpu {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // tile of the pair kernel
 constexpr int PO = 8;   // outer terms per wave (SGPR operand)
 constexpr int PJ = 4;   // inner terms per lane: i = ibase + 64*b + lane

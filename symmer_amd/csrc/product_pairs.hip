@@ -187,7 +187,6 @@ __global__ __launch_bounds__(256) void k_mul_coeff(const u64 *__restrict__ It, i
         if (full_o) {
 #pragma unroll
             for (int a = 0; a < PO; ++a) {
-                typedef double f64x2 __attribute__((ext_vector_type(2)));
                 const f64x2 w = {v[a].x, v[a].y};
                 __builtin_nontemporal_store(w, reinterpret_cast<f64x2 *>(dst + (i64)a * Ni));   // streamed out: keep the operands in L2
             }

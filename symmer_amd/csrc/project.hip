@@ -16,8 +16,6 @@
 
 namespace symgpu {
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 static int grid_of(i64 n, int block = 256, int cap = 65535) {
     i64 g = (n + block - 1) / block;
     if (g < 1) g = 1;

@@ -26,8 +26,6 @@
 
 namespace symgpu {
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 constexpr int CHAIN_SEG = 40;                     // rotations per segment: 5 sort passes of 8 bits
 constexpr int CHAIN_IDX_BITS = 22;
 

@@ -322,7 +322,6 @@ __global__ __launch_bounds__(256) void k_cchain_move(const u32x4 *__restrict__ r
         const i64 t = t0 + threadIdx.x;
         const u32 pos = s_flag[threadIdx.x] ? a_before : s_sum[1] + (u32)(t - a_before);
         s_pos[threadIdx.x] = pos;
-        typedef double f64x2 __attribute__((ext_vector_type(2)));
         reinterpret_cast<f64x2 *>(out_coeff)[pos] = reinterpret_cast<const f64x2 *>(nc)[t];
     }
     __syncthreads();

@@ -3,7 +3,8 @@
 //   rotate_analyze.hip      flags + phase exponents of every row (k_rot_analyze*), join-table insert, the persistent join table
 //   rotate_fast.hip         hash join (non-Clifford) and the Clifford fast path: match / classify, scan, write
 //   rotate_general.hip      general path: stacked operator + cleanup (operators with duplicate rows, SYMGPU_ROTATE_GENERAL)
-//   rotate_resident.hip     the whole rotation as one persistent launch
+//   rotate_resident.hip     the whole rotation as one persistent launch: its plan and the host stages of a call
+//   rotate_resident_kernel.hip  ... its kernel, phase by phase, and the launch (the two share rotate_resident.h)
 //   rotate_chain.hip        a run of Clifford rotations with the rows in registers
 //   rotate_chain_forms.hip  the other forms of a run: LDS-resident, single workgroup, two and four launches per rotation
 //   rotate_driver.hip       switches, plans, C ABI
@@ -12,8 +13,6 @@
 #include <type_traits>
 
 namespace symgpu {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Generation-tagged entries of the persistent join table (Context::rot_table): [tag = hash >> 32 | generation : 10 | row + 1 : 22].
 struct JoinTable {
@@ -26,7 +25,6 @@ __device__ __forceinline__ u64 mix64(u64 h) { h ^= h >> 33; h *= 0xff51afd7ed558
 __device__ __forceinline__ u32 jt_gen(u64 v) { return (u32)(v >> 22) & 1023u; }
 __device__ __forceinline__ i64 jt_row(u64 v) { return (i64)(v & 0x3FFFFFULL) - 1; }
 
-
 // The rotation's Pauli row Q BY VALUE in the kernel arguments (rows of <= 64 words): no host-to-device copy in front of a rotation.
 struct QArg { u64 w[64]; };
 
@@ -38,7 +36,6 @@ __device__ __forceinline__ void phase_mul(double re, double im, int e, double &o
         default: ore = im; oim = -re; break;
     }
 }
-
 
 // lane exchange inside an aligned group of WQ lanes that holds one row, 16 bytes per lane (X words in the lower, Z words in the upper half)
 template <int CTRL> __device__ __forceinline__ u32 rot_dpp(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); }
@@ -154,10 +151,22 @@ int rotate_clifford_fast(RotationRun &r);                     // Clifford, rows 
 // rotate_general.hip: stacked operator + cleanup, rows analysed
 int rotate_general(RotationRun &r);
 
-// rotate_resident.hip: the whole rotation as ONE persistent launch with the operator's rows resident in LDS.  *done = 0: not
-// applicable (operator too large, duplicate status unknown, no cached hashes ...) or verification failed — take the other paths.
+// rotate_resident.hip: the whole rotation as ONE persistent launch, each workgroup keeping its block of R rows on the chip.
+// Where the rows of a block stay between the one read and the write: in LDS; in LDS but for two 1,024-chunk rounds of the load that stay in
+// registers; or in memory, read a second time when they are written out (only the 26 bytes of per-row state are in LDS then).
+enum class ResidentForm { Lds, Registers, RowsInMemory };
+struct ResidentPlan {
+    bool applicable = false;                               // the operator qualifies (what the process state may still veto: rotate_resident_try)
+    ResidentForm form = ResidentForm::Lds;
+    int G = 0, R = 0;                                      // workgroups, rows of each
+    int nreg = 0, hbm = 0, lds_bytes = 0;                  // res_layout's arguments for the form, and its total
+    int GA = 1;                                            // lanes per row where rows are analysed from LDS or memory
+};
+// pure: no HIP call, no context.  dup_free: symgpu_op_s::dup_free; num_cu: compute units of the device
+ResidentPlan plan_resident(i64 T, int Wq, bool dup_free, int clifford_k, int num_cu, const RotateSwitches &sw);
+// *done = 0: switched off, disabled in this process, or the launch reported a failed verification or a time-out — take the other paths.
 int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double sin_t, int clifford_k, double thr, const RotateSwitches &sw,
-                        symgpu_op_t *out, int *all_commute, int *done);
+                        const ResidentPlan &plan, symgpu_op_t *out, int *all_commute, int *done);
 int rotate_resident_trace(u64 *out, int max_wgs, int *n_wgs);   // phase stamps of the last traced launch (SYMGPU_RES_TRACE=1)
 
 // A run of Clifford rotations of a clean operator (symgpu_rotate_clifford_chain_dev): `a` holds a copy of the input, `b` is a second operator

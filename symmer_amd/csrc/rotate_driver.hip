@@ -53,7 +53,7 @@ static RotateSwitches read_rotate_switches(bool chain) {
 // call on is found at run time (a failed verification of the one-launch kernel, duplicate rows found by the join or the check).
 struct RotationPlan {
     bool fits_join;          // the 22-bit row index of a join-table entry holds every row
-    bool resident;           // one persistent launch (rotate_resident_try decides itself whether the operator qualifies)
+    ResidentPlan resident;   // one persistent launch, if the operator qualifies: geometry and residency form
     bool join;               // non-Clifford: hash join
     bool dup_check;          // odd-k Clifford of an operator not known to be duplicate-free: join-table insert and read-back first
     bool clifford_fast;      // Clifford: classify, scan, write (unless the check found duplicate rows)
@@ -67,7 +67,7 @@ static RotationPlan plan_rotation(symgpu_op_t in, int clifford_k, const RotateSw
     // only the same thing for an operator without duplicate rows
     const bool may_merge = clifford && (clifford_k & 1) && !in->dup_free;
     pl.fits_join = in->T < JOIN_MAX_T;
-    pl.resident = !sw.general;
+    if (!sw.general) pl.resident = plan_resident(in->T, in->Wq, in->dup_free != 0, clifford_k, ctx().num_cu, sw);
     pl.join = !clifford && !sw.general && pl.fits_join;
     pl.dup_check = may_merge && !sw.general && pl.fits_join;
     pl.clifford_fast = clifford && !sw.general && in->T <= SCAN_MAX_T && (!may_merge || pl.fits_join);   // too large to check: merging path
@@ -161,8 +161,8 @@ int symgpu_rotate_single_dev(symgpu_op_t in, const uint64_t *q_row_host, double 
     const RotateSwitches sw = read_rotate_switches(false);
     const RotationPlan pl = plan_rotation(in, clifford_k, sw);
     int done = 0;
-    if (pl.resident) {
-        SG_TRY(rotate_resident_try(in, q_row_host, cos_t, sin_t, clifford_k, thr, sw, out, all_commute, &done));
+    if (pl.resident.applicable) {
+        SG_TRY(rotate_resident_try(in, q_row_host, cos_t, sin_t, clifford_k, thr, sw, pl.resident, out, all_commute, &done));
         if (done) return SYMGPU_OK;
     }
     RotationRun r{in, q_row_host, cos_t, sin_t, thr, clifford_k, sw, out, all_commute};

@@ -148,7 +148,6 @@ __global__ void k_rotf_write(const u32x4 *__restrict__ rows, const u32x4 *__rest
         const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
         if (t >= T) return;
         const uint8_t k = cls[t];
-        typedef double f64x2 __attribute__((ext_vector_type(2)));
         if (k & 3) {
             const i64 d = (k & 1) ? baseC + pos_self[t] : baseA + pos_self[t];
             reinterpret_cast<f64x2 *>(out_coeff)[d] = reinterpret_cast<const f64x2 *>(selfc)[t];

@@ -18,8 +18,6 @@
 
 namespace symgpu {
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 constexpr int CSR_WG = 256;                       // threads per workgroup (count pass: one row each)
 constexpr int CSR_TILE = 256;                     // sorted terms staged in LDS per round
 constexpr int CSR_SLOT_BYTES = 20;                // value (16 B) + column (4 B)

@@ -374,3 +374,88 @@ def plan_chain(T, wq, c, chain_reg=True, local_t=None):
 def register_chunks(T, wq):
     """Chunks per lane of k_cchain_reg (rotate_chain.hip clifford_chain_registers)."""
     return (4 if wq == 32 else 2) if T * wq // 128 >= 8192 else 1
+
+
+# ---------------------------------------------------------------- the one-launch rotation's plan, restated --------------------------------
+RES_FORMS = ('Lds', 'Registers', 'RowsInMemory')                      # ResidentForm of rotate_common.h; symgpu_debug_counter 33 / 34 / 35
+RES_NAMES = ('RES_THREADS', 'RES_MAX_WG', 'RES_LDS_MAX', 'RES_MIN_ROWS', 'RES_MAX_R', 'RES_REG_ROUNDS', 'RES_REG_MAX_WQ', 'RES_MAX_W', 'JOIN_MAX_T')
+
+
+def resident_constants(text):
+    """The limits of rotate_resident.h and JOIN_MAX_T of rotate_common.h from the source text (values written as a number, as a product of
+    two numbers, or as ((i64)1 << b) - 1)."""
+    import re
+    out = {}
+    for name in RES_NAMES:
+        m = re.search(r'constexpr\s+(?:int|i64|u32|size_t)\s+' + name + r'\s*=\s*([^;]+);', text)
+        if not m:
+            continue
+        expr = m.group(1).strip()
+        shift = re.fullmatch(r'\(\(i64\)1 << (\d+)\) - 1', expr)
+        prod = re.fullmatch(r'(\d+) \* (\d+)', expr)
+        if shift:
+            out[name] = (1 << int(shift.group(1))) - 1
+        elif prod:
+            out[name] = int(prod.group(1)) * int(prod.group(2))
+        elif expr.isdigit():
+            out[name] = int(expr)
+    return out
+
+
+def res_layout_total(R, wq, nreg, hbm, c):
+    """res_layout(...).total of rotate_resident.h: the LDS bytes of a workgroup that owns R rows of wq chunks."""
+    chunks = 0 if hbm else max(R * wq - nreg * c['RES_THREADS'], 0)
+    o = chunks * 16 + R * (16 + 4 + 4 + 1 + 1)                      # rows; coefficient, join state / rank, rank of the new row, info, class
+    o = (o + 15) & ~15
+    return o + c['RES_MAX_W'] * 8 + 256 * 8 + 32 * 4                  # Q, per-(pass, wavefront) counts, the block's words
+
+
+def plan_resident(T, wq, c, dup_free=True, k=-1, num_cu=256, hbm=1):
+    """plan_resident of rotate_resident.hip: None where the operator does not qualify, else (form, G, R).  k: clifford_k (-1: not a
+    Clifford angle); hbm: the value of SYMGPU_ROT_HBM (1 if unset)."""
+    if T < 1 or 2 * wq > c['RES_MAX_W'] or T >= c['JOIN_MAX_T']:
+        return None
+    if (k < 0 or (k & 1)) and not dup_free:
+        return None
+    G = min(-(-T // c['RES_MIN_ROWS']), num_cu, c['RES_MAX_WG'])
+    R = -(-T // G)
+    G = -(-T // R)
+    if R > c['RES_MAX_R']:
+        return None
+    form, total = 'Lds', res_layout_total(R, wq, 0, 0, c)
+    if total > c['RES_LDS_MAX'] and wq <= c['RES_REG_MAX_WQ'] and (wq & (wq - 1)) == 0:
+        form, total = 'Registers', res_layout_total(R, wq, c['RES_REG_ROUNDS'], 0, c)
+    if (total > c['RES_LDS_MAX'] and hbm != 0) or hbm == 2:
+        form, total = 'RowsInMemory', res_layout_total(R, wq, 0, 1, c)
+    if total > c['RES_LDS_MAX']:
+        return None
+    return form, G, R
+
+
+def resident_header_text():
+    import os
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'symmer_amd', 'csrc')
+    return open(os.path.join(csrc, 'rotate_resident.h')).read() + open(os.path.join(csrc, 'rotate_common.h')).read()
+
+
+def device_cu_count():
+    """Compute units of the current device (GPU tests): the count symgpu_device_name reports, which is the property Context::num_cu is read from."""
+    import ctypes, re
+    from symmer_amd import _lib
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.lib().symgpu_device_name(ctypes.addressof(buf), 256))
+    m = re.search(r'(\d+) CUs\)$', buf.value.decode())
+    assert m and int(m.group(1)) >= 1, buf.value
+    return int(m.group(1))
+
+
+def resident_counters():
+    """symgpu_debug_counter [1, 2, 33, 34, 35]: one-launch rotations completed, failed, and launched in the LDS / registers / rows-in-memory form."""
+    import ctypes
+    from symmer_amd import _lib
+    v = ctypes.c_int64(-1)
+    out = []
+    for which in (1, 2, 33, 34, 35):
+        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
+        out.append(v.value)
+    return np.array(out)

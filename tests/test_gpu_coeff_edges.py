@@ -13,6 +13,7 @@ from symmer_amd import PauliwordOp, kernels
 from oracle import oracle_np as onp
 from oracle import oracle_c as oc
 from _golden import family, as_bool
+import _rotation_families as fam
 
 pytestmark = pytest.mark.gpu
 
@@ -107,6 +108,7 @@ def test_rotation_edges(case, path, monkeypatch):
     _set(monkeypatch, ROT_PATHS[path])
     symp, coeff, q = as_bool(case['in_symp']), np.asarray(case['in_coeff'], dtype=complex), as_bool(case['q'])
     ang = np.array(float(case['angle']))
+    forms_before = fam.resident_counters()
     Q = PauliwordOp(q.reshape(1, -1), [1])
     zs = not _clifford(ang)
     us, uc = _first_rows(symp, coeff)
@@ -140,6 +142,11 @@ def test_rotation_edges(case, path, monkeypatch):
     cs, cc = onp.cleanup_op(us, uc)
     R = PauliwordOp(us, uc).cleanup()._rotate_by_single_Pword(Q, ang)
     assert_bits(R.symp_matrix, R.coeff_vec, *onp.rotate_by_single_pword(cs, cc, q, ang), what=path + ', after cleanup', zero_sign=zs)
+    # the form of every one-launch rotation above (symgpu_debug_counter 33 / 34 / 35 against 1 + 2): rows in LDS at these sizes, left in
+    # memory where that is forced, none on the general path; the cleaned operator's rotation is one of them
+    done, failed, lds, regs, mem = fam.resident_counters() - forms_before
+    assert [lds, regs, mem] == {'resident': [done + failed, 0, 0], 'general': [0, 0, 0], 'rows in memory': [0, 0, done + failed]}[path], (path, done, failed, lds, regs, mem)
+    assert path == 'general' or cs.shape[0] == 0 or done + failed >= 1, path
 
 
 def test_rotation_chain_edges():

@@ -233,11 +233,17 @@ def test_cfg2_full_size_rotations_against_the_oracle():
         _lib.check(_lib.lib().symgpu_debug_counter(1, ctypes.addressof(cnt)))
         return cnt.value
 
+    import _rotation_families as fam
+    res_c, cus = fam.resident_constants(fam.resident_header_text()), fam.device_cu_count()
+
     def check(dev_in, symp_in, c_in, q, qpk, ang, exact):
-        before = one_launch_count()
+        before, forms_before = one_launch_count(), fam.resident_counters()[2:]
         res, allc = kernels.rotate_single_dev(dev_in, qpk, ang)
         assert not allc
         took = one_launch_count() - before
+        # the residency form of the launch (symgpu_debug_counter 33 / 34 / 35) is the one the restated plan gives for this device
+        planned = fam.plan_resident(symp_in.shape[0], fam.wq_of(n), res_c, num_cu=cus)
+        assert list(fam.resident_counters()[2:] - forms_before) == [int(planned is not None and planned[0] == f) for f in fam.RES_FORMS], planned
         r, c = res.download()
         er, ec = onp.rotate_by_single_pword(symp_in, c_in, q, ang)
         assert r.shape[0] == er.shape[0], (r.shape, er.shape)
@@ -257,6 +263,8 @@ def test_cfg2_full_size_rotations_against_the_oracle():
     # second rotation, of the 1.5e5-term result: above the kernel's LDS capacity at 1,000 qubits (rows spill to registers)
     res3, er3, _, took3 = check(res1, er1, ec1, qs[2], qp[2], -1.1, False)
     assert took3 == 1, 'the register-spill form of the one-launch kernel did not take the 150,000-term operator'
+    planned3 = fam.plan_resident(er1.shape[0], fam.wq_of(n), res_c, num_cu=cus)
+    assert cus < 256 or planned3[0] == 'Registers', planned3       # (check() has compared the plan with counter 34)
     assert res3.n_terms > 2.1 * N
     for h in (res1, res3, clean):
         h.free()
@@ -286,12 +294,23 @@ def test_one_launch_rotation_with_the_rows_left_in_memory(n, N, monkeypatch):
         _lib.check(_lib.lib().symgpu_debug_counter(1, ctypes.addressof(cnt)))
         return cnt.value
 
+    import _rotation_families as fam
+    res_c, cus = fam.resident_constants(fam.resident_header_text()), fam.device_cu_count()
+
+    def form_launched(T, forms_before):
+        """the launch since `forms_before` had the residency form (symgpu_debug_counter 33 / 34 / 35) of the restated plan for this device"""
+        planned = fam.plan_resident(T, fam.wq_of(n), res_c, num_cu=cus)
+        assert planned is not None and list(fam.resident_counters()[2:] - forms_before) == [int(planned[0] == f) for f in fam.RES_FORMS], planned
+        return planned[0]
+
     q1 = rng.random(2 * n) < 0.3; q2 = rng.random(2 * n) < 0.3
     for q, ang, exact in ((q1, 0.3, False), (q2, np.pi / 2, True)):
         qpk = packing.pack_rows(q.reshape(1, -1))[0]
-        before = one_launch_count()
+        before, forms_before = one_launch_count(), fam.resident_counters()[2:]
         res, allc = kernels.rotate_single_dev(clean, qpk, ang)
         assert not allc and one_launch_count() - before == 1, 'the one-launch kernel did not take the operator'
+        form = form_launched(symp0.shape[0], forms_before)
+        assert cus < 256 or form == ('Lds' if (n, N) == (3000, 8000) else 'RowsInMemory'), form
         r, c = res.download()
         monkeypatch.setenv('SYMGPU_ROT_RESIDENT', '0')
         res_m, _ = kernels.rotate_single_dev(clean, qpk, ang)
@@ -304,9 +323,10 @@ def test_one_launch_rotation_with_the_rows_left_in_memory(n, N, monkeypatch):
         assert np.array_equal(c, ec) if exact else np.allclose(c, ec, rtol=0, atol=1e-12)
         if not exact:                                             # the grown operator (hashes handed on by the kernel) once more
             q3 = rng.random(2 * n) < 0.3
-            before = one_launch_count()
+            before, forms_before = one_launch_count(), fam.resident_counters()[2:]
             res2, _ = kernels.rotate_single_dev(res, packing.pack_rows(q3.reshape(1, -1))[0], -0.7)
             assert one_launch_count() - before == 1
+            form_launched(er.shape[0], forms_before)
             r2, c2 = res2.download()
             er2, ec2 = onp.rotate_by_single_pword(er, ec, q3, -0.7)
             assert np.array_equal(r2, packing.pack_rows(er2)) and np.allclose(c2, ec2, rtol=0, atol=1e-12)

@@ -1220,9 +1220,21 @@ def test_jordan_and_reindex_golden(case):
 @pytest.mark.parametrize('case', family('rotate')[::3])
 def test_rotate_golden_rows_left_in_memory(case, monkeypatch):
     """SYMGPU_ROT_HBM=2 makes the one-launch rotation kernel leave the rows in memory (the form operators beyond the chip's LDS take,
-    csrc/rotate_resident.hip) whatever the operator's size: the reference-generated cases, every row length among them."""
+    csrc/rotate_resident_kernel.hip) whatever the operator's size: the reference-generated cases, every row length among them.  Every one-launch
+    rotation of the case (completed or failed) was launched in that form and in no other: symgpu_debug_counter 35 against 1 + 2, 33 and 34."""
+    import _rotation_families as fam
     monkeypatch.setenv('SYMGPU_ROT_HBM', '2')
+    before = fam.resident_counters()
     test_rotate_golden(case)
+    done, failed, lds, regs, mem = fam.resident_counters() - before
+    assert (lds, regs) == (0, 0) and mem == done + failed, (done, failed, lds, regs, mem)
+    # a single rotation by an even multiple of pi/2 qualifies whatever is known about duplicate rows (no row can merge): it was launched
+    if not int(case['chain']):
+        T, n = case['in_symp'].shape[0], case['in_symp'].shape[1] // 2
+        k = kernels.rotation_args(float(case['angle']))[2]
+        planned = fam.plan_resident(T, fam.wq_of(n), fam.resident_constants(fam.resident_header_text()), dup_free=False, k=k, num_cu=fam.device_cu_count(), hbm=2)
+        if planned is not None:
+            assert planned[0] == 'RowsInMemory' and done + failed >= 1, (planned, done, failed)
 
 
 @pytest.mark.parametrize('case', family('rotate')[::3])

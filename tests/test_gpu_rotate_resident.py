@@ -1,4 +1,4 @@
-"""The one-launch, LDS-resident rotation kernel (symmer_amd/csrc/rotate_resident.hip) against the multi-launch paths (bit for bit:
+"""The one-launch, LDS-resident rotation kernel (symmer_amd/csrc/rotate_resident_kernel.hip, planned and launched from rotate_resident.hip) against the multi-launch paths (bit for bit:
 rows, row order, coefficients) and against the NumPy oracle of PauliwordOp._rotate_by_single_Pword (reference base.py:1090-1161).
 The kernel only takes operators whose duplicate status and row hashes are known, i.e. from the second rotation of a handle on."""
 import ctypes
@@ -73,6 +73,10 @@ def test_resident_rotation_equals_multilaunch_and_oracle(n, T, monkeypatch):
     up.free()
     r0, c0 = op.download()
     assert np.array_equal(r0, packing.pack_rows(symp)) and np.array_equal(c0, c)
+    # which residency form the launches take (symgpu_debug_counter 33 / 34 / 35): the plan, restated for this device — rows in LDS at these sizes
+    planned = fam.plan_resident(symp.shape[0], fam.wq_of(n), fam.resident_constants(fam.resident_header_text()), num_cu=fam.device_cu_count())
+    assert planned is not None and planned[0] == 'Lds', planned
+    forms_before = [counter(33 + i) for i in range(3)]
     for ang in ANGLES:
         ra, rb = run_both(op, qp, ang, monkeypatch)
         er, ec = onp.rotate_by_single_pword(symp, c, q, ang)
@@ -88,6 +92,8 @@ def test_resident_rotation_equals_multilaunch_and_oracle(n, T, monkeypatch):
         else:
             keep_d, keep_o = np.abs(rb[1]) > TOL, np.abs(ec) > TOL
             assert np.array_equal(rb[0][keep_d], got[keep_o]) and np.allclose(rb[1][keep_d], ec[keep_o], rtol=0, atol=TOL)
+    launched = [counter(33 + i) - forms_before[i] for i in range(3)]
+    assert launched == [len(ANGLES) if f == planned[0] else 0 for f in fam.RES_FORMS], (launched, planned)   # one launch per resident call
     op.free()
 
 

@@ -214,3 +214,61 @@ def test_header_constants_and_plan():
 
 def T_LIMIT(c):
     return 1 << c['CHAIN_IDX_BITS']
+
+
+# ---------------------------------------------------------------- the one-launch rotation's plan -------------------------------------------
+def resident_constants():
+    return fam.resident_constants(fam.resident_header_text())
+
+
+def last_rows_that_fit(wq, nreg, hbm, c):
+    """The largest block R whose layout fits RES_LDS_MAX — both sides of the boundary checked against the restated layout sum."""
+    R = 1
+    while fam.res_layout_total(R + 1, wq, nreg, hbm, c) <= c['RES_LDS_MAX']:
+        R += 1
+    assert fam.res_layout_total(R, wq, nreg, hbm, c) <= c['RES_LDS_MAX'] < fam.res_layout_total(R + 1, wq, nreg, hbm, c)
+    return R
+
+
+def test_resident_plan_at_its_edges():
+    """plan_resident (rotate_resident.hip), restated on the constants of rotate_resident.h, for a device of 256 compute units: geometry and
+    residency form at every edge the C++ has.  The sizes follow from the layout: a row of wq chunks takes 16 wq + 26 bytes of LDS, a
+    workgroup 3,200 bytes more, and the Registers form holds 2 x 1,024 chunks (32,768 bytes) outside it."""
+    c = resident_constants()
+    assert set(c) == set(fam.RES_NAMES), c
+    assert (c['RES_LDS_MAX'], c['RES_MIN_ROWS'], c['RES_MAX_WG'], c['RES_MAX_W'], c['JOIN_MAX_T']) == (160 * 1024, 64, 256, 128, (1 << 22) - 1)
+    plan = lambda T, wq, **kw: fam.plan_resident(T, wq, c, **kw)
+    # one workgroup up to RES_MIN_ROWS rows, then two; beyond 256 x 64 rows the blocks grow
+    assert [plan(T, 16) for T in (1, 63, 64, 65)] == [('Lds', 1, 1), ('Lds', 1, 63), ('Lds', 1, 64), ('Lds', 2, 33)]
+    assert plan(256 * 64, 16) == ('Lds', 256, 64) and plan(256 * 64 + 1, 16) == ('Lds', 253, 65)
+    # LDS -> registers -> rows in memory for rows of a power-of-two number of chunks <= 32
+    for wq, r_lds, r_reg in ((16, 569, 685), (32, 298, 359)):
+        assert last_rows_that_fit(wq, 0, 0, c) == r_lds and last_rows_that_fit(wq, c['RES_REG_ROUNDS'], 0, c) == r_reg
+        assert plan(256 * r_lds, wq) == ('Lds', 256, r_lds) and plan(256 * r_lds + 1, wq) == ('Registers', 256, r_lds + 1)
+        assert plan(256 * r_reg, wq) == ('Registers', 256, r_reg) and plan(256 * r_reg + 1, wq) == ('RowsInMemory', 256, r_reg + 1)
+        # SYMGPU_ROT_HBM=0 refuses what the default takes; =2 forces the form at any size
+        assert plan(256 * r_reg + 1, wq, hbm=0) is None and plan(256 * r_reg, wq, hbm=0) == ('Registers', 256, r_reg)
+        assert plan(1, wq, hbm=2) == ('RowsInMemory', 1, 1) and plan(256 * r_lds, wq, hbm=2) == ('RowsInMemory', 256, r_lds)
+    # 3 chunks a row: not a power of two, from LDS straight to rows in memory
+    r3 = last_rows_that_fit(3, 0, 0, c)
+    assert r3 == 2170 and plan(256 * r3, 3) == ('Lds', 256, r3) and plan(256 * r3 + 1, 3) == ('RowsInMemory', 256, r3 + 1)
+    # 64 chunks (128 words) a row is the longest; no register form above 32 chunks
+    r64 = last_rows_that_fit(64, 0, 0, c)
+    assert r64 == 152
+    assert plan(1, 64) == ('Lds', 1, 1) and plan(1, 65) is None
+    assert plan(256 * r64, 64) == ('Lds', 256, r64) and plan(256 * r64 + 1, 64) == ('RowsInMemory', 255, r64 + 1)   # (G re-derived: 255 blocks of 153 rows)
+    # The per-row state alone bounds the block: 26 bytes a row.  RES_MAX_R (16,384 rows: 16 ranking passes, 16-bit counts) and JOIN_MAX_T lie
+    # beyond that bound at every width, so a block of RES_MAX_R rows is refused by the layout already (425,984 bytes), as is the next
+    r_mem = last_rows_that_fit(1, 0, 1, c)
+    assert r_mem == 6178 and all(last_rows_that_fit(wq, 0, 1, c) == r_mem for wq in (3, 16, 64))
+    assert plan(256 * r_mem, 16) == ('RowsInMemory', 256, r_mem) and plan(256 * r_mem + 1, 16) is None
+    assert c['RES_MAX_R'] == 16384 and fam.res_layout_total(c['RES_MAX_R'], 1, 0, 1, c) > c['RES_LDS_MAX']
+    assert plan(c['RES_MAX_R'], 1, num_cu=1) is None and plan(c['RES_MAX_R'] + 1, 1, num_cu=1) is None
+    assert plan(256 * c['RES_MAX_R'] - 3, 1) is None                                # (R = 16,384 with T < JOIN_MAX_T)
+    assert plan(c['JOIN_MAX_T'], 1) is None and plan(c['JOIN_MAX_T'] - 1, 1) is None
+    # fewer compute units: fewer, larger blocks
+    assert plan(20000, 16, num_cu=64) == ('Lds', 64, 313) and plan(20000, 16, num_cu=304) == ('Lds', 254, 79)
+    # rows may merge in a non-Clifford rotation and for odd k: only for an operator known to be free of duplicates
+    for k, ok in ((-1, False), (1, False), (3, False), (0, True), (2, True)):
+        assert (plan(1000, 16, dup_free=False, k=k) is not None) == ok, k
+        assert plan(1000, 16, dup_free=True, k=k) == ('Lds', 16, 63), k

@@ -8,6 +8,8 @@ export TMPDIR=/tmp
 tag=${1:-r05}; wl=${2:-rotation}
 case $wl in
   mul_cleanup) short=cfg3; like='%k_emit_fused%'; srcs="cleanup.hip";;
+  # (the list bench.py hashes for this workload; the kernel itself is in rotate_resident_kernel.hip and rotate_resident.h: retake the
+  #  profile after an edit there, the recorded hash does not notice it)
   rotation)    short=rotation; like='%k_rot_resident%'; srcs="rotate_resident.hip";;
   gf2)         short=gf2; like='%k_sweep_m4r<1>%'; srcs="gf2.hip";;
   adjacency)   short=adjacency; like='%k_commutes_m4r%'; srcs="commute_m4r.hip commute_m4r7.hip";;
