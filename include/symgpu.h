@@ -302,6 +302,31 @@ typedef struct symgpu_csr_s *symgpu_csr_t;
 int symgpu_to_csr_count(symgpu_op_t op, int n_qubits, int64_t *nnz, int64_t *fill_scratch_bytes, symgpu_csr_t *plan);
 int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *indptr, int index_bytes);
 
+/* ---- f6: PauliwordOp.from_matrix (base.py:239-425), the inverse of f5: the Pauli decomposition of a 2^n x 2^n matrix M, n_qubits 1 .. 31
+ * (csrc/pauli_decomp.hip).  With the conventions of f5 (qubit 0 the MOST significant bit of b, x, z):
+ *   c(x, z) = i^{|x & z| mod 4} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]
+ * The sum is the radix-2 butterfly on the XOR-diagonal d_x[b] = M[b, b ^ x]: stage s = 0 .. n-1 combines the two elements whose indices
+ * differ in bit s, a' = a + b, b' = a - b (a: bit clear), per component in IEEE double; then one multiplication by 2^-n and i^k as a
+ * component swap: every form of the transform, and any restatement with these additions, agrees bit for bit.
+ * symgpu_from_matrix_dense   matrix: complex128 [2^n][2^n], C order (n_qubits <= 16).
+ * symgpu_from_matrix_csr     data complex128 [nnz], indices [nnz], indptr [2^n + 1], both of index_bytes = 4 (int32) or 8 (int64); no entry
+ *   may be stored twice (canonical CSR); only the diagonals x = row ^ col of stored entries are transformed, absent entries are +0.0.
+ * Basis (optional): basis_x / basis_z uint64 [K], the X and Z parts of K terms as n-bit integers; K = 0 means all 4^n terms.
+ *   K = 0: *out = a new resident operator (Wq = 1, marked duplicate-free) holding every coefficient whose two components are not both
+ *     +-0 (NaN and inf are kept), in ascending (x, z) order, x the high part; *n_out = its term count; coeff_out is not used.
+ *   K > 0: coeff_out complex128 [K] on the host = c(basis_x[k], basis_z[k]) in basis order, zeros included; out / n_out are not used.
+ * *form (may be NULL) = SYMGPU_PAULI_ONE_PASS: every diagonal (2^n <= 2^13 elements = 128 KiB) was transformed in LDS in one launch, or
+ * SYMGPU_PAULI_TWO_PASS: the low tile bits in LDS tiles, the bits above them across the tiles in further launches.
+ * SYMGPU_PAULI_TILE_BITS=t (3 .. 13, read on every call) sets the tile size, so that a small matrix takes the two-pass form.
+ * (number of diagonals) x 2^n must stay below 2^31 slots of 16 bytes (SYMGPU_E_INVALID); the device memory is checked before it is
+ * allocated (SYMGPU_E_NOMEM).  Every device scratch buffer is freed before the call returns, also on failure. */
+#define SYMGPU_PAULI_ONE_PASS 1
+#define SYMGPU_PAULI_TWO_PASS 2
+int symgpu_from_matrix_dense(const double *matrix, int n_qubits, const uint64_t *basis_x, const uint64_t *basis_z, int64_t K, symgpu_op_t *out,
+                             int64_t *n_out, double *coeff_out, int *form);
+int symgpu_from_matrix_csr(const double *data, const void *indices, const void *indptr, int index_bytes, int64_t nnz, int n_qubits,
+                           const uint64_t *basis_x, const uint64_t *basis_z, int64_t K, symgpu_op_t *out, int64_t *n_out, double *coeff_out, int *form);
+
 /* ---- e: multi-GPU (one process per GPU; RCCL over xGMI) ------------------------------------------- */
 #define SYMGPU_UNIQUE_ID_BYTES 128
 int symgpu_comm_available(void);                                                /* librccl loadable? (no device, no collective) */

@@ -104,6 +104,8 @@ SIGNATURES = {
     'symgpu_state_inner_dev': [P, P, P],
     'symgpu_to_csr_count': [P, c_int, P, P, PP],
     'symgpu_to_csr_fill': [P, P, P, P, c_int],
+    'symgpu_from_matrix_dense': [P, c_int, P, P, c_i64, PP, P, P, P],
+    'symgpu_from_matrix_csr': [P, P, P, c_int, c_i64, c_int, P, P, c_i64, PP, P, P, P],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

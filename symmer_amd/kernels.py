@@ -571,6 +571,54 @@ def to_csr(devop, n_qubits):
     return data, indices, indptr
 
 
+# ---- PauliwordOp.from_matrix: Pauli decomposition on the device (csrc/pauli_decomp.hip) -----------------------------------------------
+PAULI_ONE_PASS, PAULI_TWO_PASS = 1, 2        # SYMGPU_PAULI_ONE_PASS / SYMGPU_PAULI_TWO_PASS: the transform form a call reports
+
+
+def _pauli_basis(basis_x, basis_z):
+    if basis_x is None:
+        return None, None, 0
+    bx, bz = np.ascontiguousarray(basis_x, dtype='<u8'), np.ascontiguousarray(basis_z, dtype='<u8')
+    assert bx.ndim == 1 and bx.shape == bz.shape
+    return bx, bz, bx.shape[0]
+
+
+def _pauli_call(fn, args, n_qubits, bx, bz, K):
+    """The tail both entry points share: (DeviceOp, n_terms, form) without a basis, (complex128[K], form) with one."""
+    out, n_out, form = ctypes.c_void_p(), c_i64(0), c_int(0)
+    coeff = np.empty(K, dtype=np.complex128) if K else None
+    rc = fn(*args, int(n_qubits), addr(bx), addr(bz), K, ctypes.byref(out), ctypes.addressof(n_out), addr(coeff), ctypes.addressof(form))
+    if rc == _lib.E_NOMEM:
+        raise MemoryError(f'from_matrix: {_lib.last_error()}')
+    check(rc)
+    if K:
+        return coeff, form.value
+    return DeviceOp(out), n_out.value, form.value
+
+
+def pauli_decompose_dense(matrix, n_qubits, basis_x=None, basis_z=None):
+    """Pauli coefficients ``c(x, z) = i^{|x & z|} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]`` of a dense ``2^n x 2^n`` matrix (qubit 0 the most
+    significant bit of b, x, z; the sum is the pinned radix-2 butterfly of ``symgpu_from_matrix_dense``).  Without a basis: a new
+    DeviceOp with every coefficient that is not (+-0, +-0) in ascending (x, z) order, its term count and the transform form that ran.
+    With ``basis_x`` / ``basis_z`` (uint64[K]): the K coefficients in basis order, zeros included, and the form."""
+    m = np.ascontiguousarray(matrix, dtype=np.complex128)
+    assert m.shape == (1 << int(n_qubits), 1 << int(n_qubits)), 'matrix must be 2^n x 2^n'
+    bx, bz, K = _pauli_basis(basis_x, basis_z)
+    return _pauli_call(_lib.lib().symgpu_from_matrix_dense, (addr(m),), n_qubits, bx, bz, K)
+
+
+def pauli_decompose_csr(data, indices, indptr, n_qubits, basis_x=None, basis_z=None):
+    """The same for a canonical CSR matrix (no duplicate entries; ``indices`` / ``indptr`` both int32 or both int64): only the
+    XOR-diagonals ``row ^ col`` that hold a stored entry are transformed."""
+    data = np.ascontiguousarray(data, dtype=np.complex128)
+    idx_dtype = np.int64 if np.dtype(indptr.dtype).itemsize == 8 or np.dtype(indices.dtype).itemsize == 8 else np.int32
+    indices, indptr = np.ascontiguousarray(indices, dtype=idx_dtype), np.ascontiguousarray(indptr, dtype=idx_dtype)
+    assert indptr.shape == ((1 << int(n_qubits)) + 1,) and indices.shape == data.shape
+    bx, bz, K = _pauli_basis(basis_x, basis_z)
+    return _pauli_call(_lib.lib().symgpu_from_matrix_csr, (addr(data), addr(indices), addr(indptr), np.dtype(idx_dtype).itemsize, data.shape[0]),
+                       n_qubits, bx, bz, K)
+
+
 # ---- cleanups that also return the first-occurrence index of every output term (hash-partitioned multi-GPU cleanup, parallel.py) ----
 def _first_index(op):
     t = op.n_terms

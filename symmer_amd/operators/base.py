@@ -1,9 +1,9 @@
 """``PauliwordOp`` — drop-in for the reference class on the symplectic hot path
 (``symmer/operators/base.py:33-1561``): same constructor, attributes, methods, exceptions and results for
 construction, ``+ - *``, ``cleanup``, commutation/adjacency, single-Pauli rotations and GF(2) generator
-routines, and ``to_sparse_matrix`` (a scipy CSR matrix built on the device, csrc/sparse_matrix.hip).  The
-data-parallel work runs in hand-written HIP kernels (``libsymgpu.so``); host code is NumPy glue only.  Out of
-scope (not on the path): ``from_matrix``, graph colouring, openfermion/qiskit converters;
+routines, ``to_sparse_matrix`` (a scipy CSR matrix built on the device, csrc/sparse_matrix.hip) and its inverse
+``from_matrix`` / ``haar_random`` (csrc/pauli_decomp.hip).  The data-parallel work runs in hand-written HIP
+kernels (``libsymgpu.so``); host code is NumPy glue only.  Out of scope (not on the path): graph colouring, openfermion/qiskit converters;
 ``QuantumState`` lives in quantum_state.py.
 """
 import warnings
@@ -232,6 +232,76 @@ class PauliwordOp:
     @classmethod
     def empty(cls, n_qubits: int) -> "PauliwordOp":
         return cls.from_dictionary({'I' * n_qubits: 0})
+
+    @classmethod
+    def from_matrix(cls, matrix, operator_basis: "PauliwordOp" = None, strategy: str = 'projector',
+                    disable_loading_bar: bool = False) -> "PauliwordOp":
+        """base.py:239-425: the Pauli decomposition of a matrix, computed on the device (csrc/pauli_decomp.hip) as one Walsh-Hadamard
+        transform per XOR-diagonal ``M[b, b ^ x]``.  ``matrix``: ``np.ndarray``, ``np.matrix`` or any ``scipy.sparse`` matrix (brought to
+        canonical CSR on the host: duplicates summed, explicit zeros dropped); ``n = ceil(log2(max(shape)))``.  Both strategies of the
+        reference name the same coefficients ``tr(P^dagger M) / 2^n`` and take the same device path; ``disable_loading_bar`` is accepted
+        and has nothing to disable.  The result holds every coefficient that is not exactly zero, in ascending order of the terms' (X, Z)
+        bits read as integers with qubit 0 most significant (the reference's order is whatever ``dok_matrix.nonzero()`` yields), and
+        stays on the device until its arrays are read.  With ``operator_basis``: the terms of ``operator_basis.copy().cleanup()`` in its
+        order with the computed coefficients, zeros dropped, and the reference's warning.
+        Deliberate divergences: a matrix that is not ``2^n x 2^n`` is zero-padded in complex, dense and sparse alike (the reference pads
+        into a real array, losing the imaginary parts, and fails on sparse input); an unknown strategy is refused with a basis too."""
+        from scipy import sparse
+        if strategy not in ('projector', 'full_basis'):
+            raise ValueError('Unrecognised strategy, must be one of full_basis or projector')
+        if isinstance(matrix, np.matrix):
+            matrix = np.asarray(matrix)
+        is_sparse = sparse.issparse(matrix)
+        if not is_sparse and not isinstance(matrix, np.ndarray):
+            raise ValueError('Unrecognised matrix type, must be one of np.array or sp.sparse.csr_matrix')
+        if len(matrix.shape) != 2 or min(matrix.shape) < 1:
+            raise ValueError(f'from_matrix: a matrix has two non-empty dimensions, got shape {matrix.shape}')
+        n_qubits = int(np.ceil(np.log2(max(matrix.shape))))
+        if n_qubits > 31:
+            raise ValueError(f'from_matrix: {n_qubits} qubits; at most 31 (row and column indices must fit an int32 index space)')
+        if n_qubits > 30 and operator_basis is None:
+            raise ValueError('Matrix too large! Will run into memory limitations.')
+        if n_qubits == 0:
+            return cls(np.zeros((1, 0), dtype=bool), [complex(matrix.toarray()[0, 0] if is_sparse else matrix[0, 0])])
+        side = 1 << n_qubits
+        bx = bz = basis = None
+        if operator_basis is not None:
+            basis = operator_basis.copy().cleanup()
+            if basis.n_qubits != n_qubits:
+                raise ValueError(f'from_matrix: the basis is defined over {basis.n_qubits} qubits, the matrix over {n_qubits}')
+            weights = np.int64(1) << np.arange(n_qubits - 1, -1, -1, dtype=np.int64)
+            bx = (basis.X_block.astype(np.int64) @ weights).astype('<u8')
+            bz = (basis.Z_block.astype(np.int64) @ weights).astype('<u8')
+        if is_sparse:
+            m = sparse.csr_matrix(matrix, dtype=np.complex128, copy=True)
+            m.sum_duplicates()
+            m.eliminate_zeros()
+            m.sort_indices()
+            if m.shape != (side, side):
+                m.resize((side, side))
+            found = kernels.pauli_decompose_csr(m.data, m.indices, m.indptr, n_qubits, bx, bz)
+        else:
+            if n_qubits > (15 if basis is None else 16):
+                raise ValueError(f'from_matrix: a dense matrix of {n_qubits} qubits; pass a scipy.sparse matrix')
+            if matrix.shape == (side, side):
+                m = np.ascontiguousarray(matrix, dtype=np.complex128)
+            else:
+                m = np.zeros((side, side), dtype=np.complex128)
+                m[:matrix.shape[0], :matrix.shape[1]] = matrix
+            found = kernels.pauli_decompose_dense(m, n_qubits, bx, bz)
+        if basis is None:
+            dev, n_terms, _ = found
+            return cls._from_device(dev, n_qubits, n_terms)
+        warnings.warn('Basis supplied MAY not be sufficiently expressive, output operator projected onto basis supplied.')
+        coeff = found[0]
+        kept = np.flatnonzero(~((coeff.real == 0) & (coeff.imag == 0)))
+        return cls(basis.symp_matrix[kept], coeff[kept])
+
+    @classmethod
+    def haar_random(cls, n_qubits: int, strategy: str = 'projector', disable_loading_bar: bool = False) -> "PauliwordOp":
+        """base.py:110-127: a Haar-random unitary of ``2^n x 2^n`` (``scipy.stats.unitary_group``) in the Pauli basis."""
+        from scipy.stats import unitary_group
+        return cls.from_matrix(unitary_group.rvs(2 ** n_qubits), strategy=strategy, disable_loading_bar=disable_loading_bar)
 
     # ---- printing / copying / ordering ---------------------------------------------------------------
     def __str__(self) -> str:
