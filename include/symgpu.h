@@ -100,7 +100,19 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * path (stack + cleanup); 32: of 31, odd-k Clifford rotations whose duplicate check found two equal rows.  Rotations completed by the
  * one-launch kernel are counted by 1 alone.  tests/test_gpu_rotation_families.py asserts through 22-32 which form and stage ran.
  * 33 / 34 / 35: one-launch rotations LAUNCHED (completed or not) with each block's rows in LDS / in LDS and registers / left in memory;
- * tests/test_gpu_rotate_resident.py and the full-size tests assert through them which form a shape took. */
+ * tests/test_gpu_rotate_resident.py and the full-size tests assert through them which form a shape took.
+ * 36 .. 47: the fused product + cleanup (symgpu_mul_cleanup*, and what is built on them), counted once per ATTEMPT of a call (a call
+ * that reseeds the row hash or repeats with the full sort counts every attempt).  36: the packed pair keys were ordered by the complete
+ * sort, no flag pass; 37 / 38: the flag pass was launched from the bucketed operand hash tables / behind the partial sort; 39: a flag pass
+ * came back with its give-up word set; 40 / 41 / 42 / 43: of 39, the hash-table pass by reason (one each for every reason it reported): a
+ * product bucket of more than 16,384 pairs / a saturated 4-bit counter / an overflowing list / an operand bucket of more than 255 terms;
+ * 44: the sort was finished on the whole array after the flag pass (most keys flagged, a give-up, or SYMGPU_CLEANUP_SUSPECTS=2); 45: the
+ * flagged keys were sorted alone; 46: the single terms were marked from one byte per pair; 47: the attempt was repeated with the full 64-bit
+ * sort (a long run of equal key prefixes that holds different keys).  Calls on 64-bit keys with an index sort (plain cleanups,
+ * SYMGPU_CLEANUP_UNPACKED=1, index fields over 32 bits) count none of 36 .. 46.  48 .. 52: calls of symgpu_mul_allpairs_dev (and of
+ * symgpu_mul_allpairs) with at least one pair to form (counted before the path runs, whether or not it succeeds), by path: rows only / phase-byte row stream / wide coefficient kernel, then rows /
+ * word-major coefficient kernel, then rows / the same beside the rows on a second stream.  tests/test_gpu_pair_flows.py and
+ * tests/test_gpu_product_coeff_stage.py assert through them which flow and path a call took. */
 int symgpu_debug_counter(int which, int64_t *value);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so

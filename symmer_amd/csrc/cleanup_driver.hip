@@ -158,7 +158,7 @@ static int cleanup_run(const CleanupRequest &rq, symgpu_op_t *out) {
             radix_sort_coop_note(hback[3], &timed_out);
             if (timed_out) continue;
         }
-        if (hback[2]) { r.pl = plan_cleanup(rq, r.sw, true); continue; }   // a long mixed prefix run: redo with a full 64-bit sort over all pairs, same seed
+        if (hback[2]) { bump_counter(47); r.pl = plan_cleanup(rq, r.sw, true); continue; }   // a long mixed prefix run: redo with a full 64-bit sort over all pairs, same seed
         ok = (hback[1] == 0);
         if (!ok) { ++r.seed; g_hash_reseeds.fetch_add(1, std::memory_order_relaxed); }   // genuine 64-bit hash collision: reseed and retry
     }

@@ -544,6 +544,7 @@ static int mark_singles_packed(CleanupRun &r) {
     const double *fl_i = r.cfloor.as<double>(), *fl_o = two_ops ? r.cfloor.as<double>() + 1 : r.cfloor.as<double>();
     if (r.sw.nofloor) fl_i = fl_o = nullptr;     // tests: every coefficient looked at
     if (pl.key_bytes) {
+        bump_counter(46);                                  // symgpu_debug_counter 46: the single terms marked from bytes
         const i64 n_groups = (Tk + 63) / 64 * 4;           // whole 64-bit words of the bitmaps
         hipLaunchKernelGGL(k_mark_bytes, dim3((unsigned)grid_for(n_groups, 256, 1 << 16)), dim3(256), 0, st, r.keys.as<u32x4>(), Tk, n_groups, Ni, ci, co,
                            pl.squared ? 1 : 0, r.rq.thr, r.rq.use_thr, r.markbits.as<unsigned short>(), r.e_lo.as<unsigned short>(), r.e_hi.as<unsigned short>(), fl_i, fl_o);
@@ -615,6 +616,7 @@ static int order_flagged(CleanupRun &r) {
     bool direct = false;
     SG_TRY(pair_dups_dev(r.hI.as<u64>(), p.Ni, r.hO_p, p.No, pl.squared, Tk, susbits.as<u64>(), sustotal + 1, &direct));
     u64 *part = r.keys.as<u64>(), *spare = r.keys2.as<u64>();
+    bump_counter(direct ? 37 : 38);                        // which flag pass this attempt launches: symgpu_debug_counter 37 / 38
     if (!direct) {
         if (pl.key_bytes) SG_TRY(pair_keys(r, false));     // (the flag pass was refused: keys after all)
         SG_TRY(radix_sort_keys_u64(r.keys.as<u64>(), r.keys2.as<u64>(), Tk, lo, hi, &a.in_tmp, a.first_hist));
@@ -643,7 +645,12 @@ static int order_flagged(CleanupRun &r) {
         SG_TRY(read_back_wait(&rb, h_sus2));
     }
     const u32 h_sus = h_sus2[0];
+    if (h_sus2[1]) {                                       // the flag pass gave up; the hash-table pass says why (the bits of k_pd_bucket / k_pair_dups)
+        bump_counter(39);
+        for (int b = 0; direct && b < 4; ++b) if ((h_sus2[1] >> b) & 1u) bump_counter(40 + b);
+    }
     if ((i64)h_sus * 16 > Tk || r.sw.suspects == 2 || h_sus2[1]) {
+        bump_counter(44);                                  // symgpu_debug_counter 44: the sort finished on the whole array
         // repeated rows all over: the last pass on the whole array after all (LSD: the order so far is its first passes; the
         // direct flag pass left the keys in index order: all passes)
         bool in_tmp2 = false;
@@ -652,6 +659,7 @@ static int order_flagged(CleanupRun &r) {
         if (in_tmp2) a.in_tmp = !a.in_tmp;
         return SYMGPU_OK;
     }
+    bump_counter(45);                                      // symgpu_debug_counter 45: the flagged keys sorted alone (none flagged: nothing to sort)
     a.sus_active = true;
     a.Tsort = h_sus;
     if (a.Tsort == 0) return SYMGPU_OK;
@@ -680,6 +688,7 @@ int cleanup_order(CleanupRun &r) {
         else SG_TRY(radix_sort_pairs_u64_u32(r.keys.as<u64>(), r.idx.as<u32>(), r.keys2.as<u64>(), r.idx2.as<u32>(), Tk, 64 - pl.nbits, 64, &a.in_tmp));
     } else if (!pl.sus_try) {
         // (small products — up to 2e5 keys, no first-pass histograms at hand —: the sort in ONE launch; its passes were three launches each)
+        bump_counter(36);                                  // symgpu_debug_counter 36: the complete sort of the packed keys, no flag pass
         bool coop_done = false;
         if (!a.first_hist) SG_TRY(radix_sort_keys_u64_small(r.keys.as<u64>(), r.keys2.as<u64>(), Tk, 64 - pl.nbits, 64, &a.in_tmp, &coop_done));
         if (coop_done) a.sus_coop = true;

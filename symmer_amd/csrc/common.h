@@ -132,7 +132,7 @@ void forget_bound_device();                // after a library (RCCL) may have ch
         if (!(_done.fetch_or(_bit) & _bit) && (expr)) _ok.fetch_or(_bit);                             \
         return (_ok.load() & _bit) != 0;                                                              \
     }())
-extern std::atomic<i64> g_counters[36];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
+extern std::atomic<i64> g_counters[53];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
                                            // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls),
                                            // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
                                            // [14] uses of a context by a call that did not hold its lock, [15] blocks panelled by the blocked GF(2)
@@ -145,7 +145,16 @@ extern std::atomic<i64> g_counters[36];    // debug counters (symgpu_debug_count
                                            // sort (rotate_chain.hip), [29] / [30] / [31] single rotations completed by the hash join / the Clifford
                                            // fast path / the general path, [32] of [31]: sent there by the duplicate check (symgpu_rotate_single_dev),
                                            // [33] / [34] / [35] one-launch rotations launched with the rows in LDS / in LDS and registers / left in
-                                           // memory (rotate_resident_kernel.hip launch_resident, nowhere else)
+                                           // memory (rotate_resident_kernel.hip launch_resident, nowhere else),
+                                           // [36] .. [47] product + cleanup, per attempt of cleanup_run (cleanup_keys.hip, one place each; [47]:
+                                           // cleanup_driver.hip): [36] packed keys ordered by the complete sort (no flag pass), [37] / [38] the flag
+                                           // pass launched from the operand hash tables / behind the partial sort, [39] a flag pass came back with
+                                           // giveup != 0, [40] .. [43] of these, the hash-table pass by reason: product bucket over 16,384 pairs /
+                                           // counter saturated / list overflow / operand bucket over 255, [44] the sort finished on the whole array
+                                           // after the flag pass, [45] the flagged keys sorted alone, [46] single terms marked from bytes,
+                                           // [47] the attempt repeated with the full 64-bit sort,
+                                           // [48] .. [52] calls of symgpu_mul_allpairs_dev by ProductPath: rows only / phase stream / wide coefficients /
+                                           // word-major, then rows / word-major beside rows (product_driver.hip, at the switch)
 inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
 inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
 inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }

@@ -6,6 +6,7 @@ import pytest
 from symmer_amd import PauliwordOp, IndependentOp, kernels, packing, _lib
 from symmer_amd.kernels import DeviceOp
 from oracle import oracle_c as oc
+import _pair_families as pfam
 
 pytestmark = pytest.mark.gpu
 
@@ -355,6 +356,19 @@ def test_product_cleanup_over_the_lazy_gate_against_the_c_oracle(shape):
     assert np.array_equal(R.coeff_vec, ec)
 
 
+def flow_counted(call):
+    """-> (result, what the product + cleanup counted: symgpu_debug_counter 36 .. 47 — None after a reseed of the row hash in this process)"""
+    def read(which):
+        v = ctypes.c_int64(0)
+        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
+        return v.value
+    flows = lambda: np.array([read(pfam.FIRST_FLOW_COUNTER + k) for k in range(len(pfam.FLOW_COUNTERS))])
+    reseeds, before = read(0), flows()
+    out = call()
+    took = (flows() - before).tolist()
+    return out, (took if reseeds == 0 and read(0) == 0 else None)
+
+
 @pytest.mark.parametrize('mode', ['default', 'sorted flag pass', 'full sort', 'give up', 'repeated rows', 'few rows', 'planted'])
 def test_cleanup_flagged_key_flow_switches(mode, monkeypatch):
     """The cleanup of products — the pairs that share a key found from the bucketed operand hash tables (round 6, pair_dups.hip) or, with
@@ -362,15 +376,22 @@ def test_cleanup_flagged_key_flow_switches(mode, monkeypatch):
     k_find_suspects), only the flagged keys sorted completely — against the C oracle above
     the 2^22-key gate: the default, the full sort of all keys (SYMGPU_CLEANUP_SUSPECTS=0), the flow giving up after the flag pass and
     finishing the last radix pass on the whole array (forced, and reached by itself on operands full of repeated rows, where nearly
-    every key has a partner; 'few rows': 3 x 2 distinct products, runs of ~10^6 equal keys — the flag pass itself gives up on a run it cannot
-    read to its end; 'planted': rows that are products of two other rows, so that a few hundred product rows occur two or three times)."""
+    every key has a partner; 'few rows': 3 x 2 distinct products, runs of ~10^6 equal keys; 'planted': rows that are products of two other
+    rows — which plants less than the name says: 60 product rows of A * A occur twice, none of A * B; operands with planted merges of
+    every multiplicity are in tests/test_gpu_pair_flows.py).
+    Every mode ran the flow it is named for (symgpu_debug_counter 36 .. 47 against the restated plan of tests/_pair_families.py): 'default'
+    and 'planted' the hash-table pass to its end, marking from bytes, the flagged keys sorted alone; 'give up' the whole array sorted behind
+    a hash-table pass that did not give up; 'repeated rows' a hash-table pass that gave up on a saturated counter (45 pairs a key).  'few rows'
+    does NOT reach k_find_suspects by default: the hash-table pass is launched and stops at an operand bucket of ~870 equal terms (over 255).
+    The run that k_find_suspects cannot read to its end is reached with SYMGPU_CLEANUP_DIRECT=0, which the mode runs as well."""
     rng = np.random.default_rng(4404)
     n, na, nb = 100, 2600, 2100
-    if mode == 'full sort': monkeypatch.setenv('SYMGPU_CLEANUP_SUSPECTS', '0')
-    if mode == 'give up': monkeypatch.setenv('SYMGPU_CLEANUP_SUSPECTS', '2')
-    if mode == 'sorted flag pass': monkeypatch.setenv('SYMGPU_CLEANUP_DIRECT', '0')
+    sw = {}
+    if mode == 'full sort': monkeypatch.setenv('SYMGPU_CLEANUP_SUSPECTS', '0'); sw = {'suspects': 0}
+    if mode == 'give up': monkeypatch.setenv('SYMGPU_CLEANUP_SUSPECTS', '2'); sw = {'suspects': 2}
+    if mode == 'sorted flag pass': monkeypatch.setenv('SYMGPU_CLEANUP_DIRECT', '0'); sw = {'direct': False}
     sa = rng.random((na, 2 * n)) < 0.3; sb = rng.random((nb, 2 * n)) < 0.3
-    if mode == 'planted':                          # a few hundred products that occur twice or three times: rows that are products of two others
+    if mode == 'planted':                          # rows that are products of two others: 60 product rows of A * A occur twice, none of A * B
         for k in range(150):
             i, j, l = rng.integers(0, na, 3)
             sa[l] = sa[i] ^ sa[j]
@@ -383,10 +404,30 @@ def test_cleanup_flagged_key_flow_switches(mode, monkeypatch):
     if mode == 'few rows':
         sa = sa[rng.integers(0, 3, na)]; sb = sb[rng.integers(0, 2, nb)]
     A = PauliwordOp(sa, dyadic(rng, na)); B = PauliwordOp(sb, dyadic(rng, nb))
+    C = pfam
     for X, Y in ((A, B), (A, A)):
-        R = X * Y
+        pl = pfam.plan_cleanup(X.n_terms, Y.n_terms, X is Y, 1e-15, **sw)             # (the operand with more terms is the inner one)
+        assert X.n_terms >= Y.n_terms and (pl['direct'] is not None) == (mode != 'sorted flag pass' and mode != 'full sort'), (mode, pfam.flow_name(pl))
+        R, took = flow_counted(lambda: X * Y)
         er, ec = oc.mul(X.packed, X.coeff_vec, Y.packed, Y.coeff_vec)
         assert np.array_equal(R.packed, er) and np.array_equal(R.coeff_vec, ec), mode
+        named = (mode, pfam.flow_name(pl), took and dict(zip(pfam.FLOW_COUNTERS, took)))
+        if took is None:
+            continue
+        if mode in ('default', 'planted', 'sorted flag pass', 'full sort'):
+            assert took[:C.C_REPEAT] == pfam.expected_counters(pl, 'alone')[:C.C_REPEAT], named
+        elif mode == 'give up':
+            assert took[:C.C_REPEAT] == pfam.expected_counters(pl, 'whole')[:C.C_REPEAT], named
+        elif mode == 'repeated rows':
+            assert took[C.C_DIRECT] == 1 and took[C.C_GIVEUP] == 1 and took[C.C_R_SAT] == 1 and took[C.C_WHOLE] == 1 and took[C.C_ALONE] == 0 and took[C.C_R_OPERAND] == 0, named
+        elif mode == 'few rows':
+            assert took[:C.C_REPEAT] == pfam.expected_counters(pl, 'whole', (C.C_R_OPERAND,))[:C.C_REPEAT], named
+            monkeypatch.setenv('SYMGPU_CLEANUP_DIRECT', '0')
+            R, took = flow_counted(lambda: X * Y)
+            monkeypatch.delenv('SYMGPU_CLEANUP_DIRECT')
+            assert np.array_equal(R.packed, er) and np.array_equal(R.coeff_vec, ec), (mode, 'DIRECT=0')
+            pl0 = pfam.plan_cleanup(X.n_terms, Y.n_terms, X is Y, 1e-15, direct=False)
+            assert took is None or took[:C.C_REPEAT] == pfam.expected_counters(pl0, 'gave up')[:C.C_REPEAT], (mode, 'DIRECT=0', dict(zip(pfam.FLOW_COUNTERS, took)))
 
 
 @pytest.mark.parametrize('planted', [False, True])

@@ -3,7 +3,10 @@ oracle.  The row kernel leaves the 2-bit phase sum of every pair, four pairs to 
 outer row per workgroup.  The shapes below end packed bytes and 256-term pieces part-full, cut the inner operand into tiles, need more
 outer rows than one launch's grid.y holds, and write a slab with o_begin > 0 into an output handle that already holds another slab.
 The slab and grid.y cases also run with the switches that select the other paths of the product (word-major or wide coefficient kernel
-followed by the plain row stream, rows only): each path has its own o_begin and batch-offset arithmetic."""
+followed by the plain row stream, rows only): each path has its own o_begin and batch-offset arithmetic; which path served a call is read from
+symgpu_debug_counter 48 .. 52 (one per ProductPath, bumped at the switch of symgpu_mul_allpairs_dev)."""
+import ctypes
+
 import numpy as np
 import pytest
 from symmer_amd import kernels, packing, _lib
@@ -22,6 +25,28 @@ def dyadic(rng, t):
 
 def gaussian(rng, t):
     return rng.standard_normal(t) + 1j * rng.standard_normal(t)
+
+
+PATHS = ('rows only', 'phase stream', 'wide coefficients, then rows', 'word-major coefficients, then rows', 'word-major coefficients beside rows')
+ROWS_ONLY, PHASE_STREAM, WIDE, WORD_MAJOR = 0, 1, 2, 3
+
+
+def path_counters():
+    v = ctypes.c_int64(0)
+    out = []
+    for which in range(48, 53):
+        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
+        out.append(v.value)
+    return np.array(out)
+
+
+def counted(call, path, what, calls=1):
+    """Run `call` and assert that it went through symgpu_mul_allpairs_dev `calls` times, on the path `path` every time."""
+    before = path_counters()
+    out = call()
+    delta = (path_counters() - before).tolist()
+    assert delta == [calls if k == path else 0 for k in range(5)], f'{what}: expected [{PATHS[path]}] x {calls}, took {dict((PATHS[k], d) for k, d in enumerate(delta) if d)}'
+    return out
 
 
 def check_pairs(rng, n, Ni, No, left):
@@ -62,7 +87,7 @@ def test_coeff_stage_more_outer_rows_than_one_grid(fused, monkeypatch):
     """70,000 outer rows: more than the 65,535 of one launch's grid.y, so the slab goes out in two launches of each kernel (fused = 0: of
     the plain row stream, behind the word-major coefficient kernel)."""
     monkeypatch.setenv('SYMGPU_PRODUCT_FUSED', fused)
-    check_pairs(np.random.default_rng(1200), 20, 3, 70000, True)
+    counted(lambda: check_pairs(np.random.default_rng(1200), 20, 3, 70000, True), PHASE_STREAM if fused == '1' else WORD_MAJOR, f'fused={fused}', calls=2)
 
 
 # the paths of symgpu_mul_allpairs_dev by environment: phase-byte stream where the row length allows it / word-major coefficient kernel +
@@ -85,14 +110,19 @@ def test_coeff_stage_slab_into_reused_handle(n, Ni, env, monkeypatch):
     out = DeviceOp.alloc(No * Ni, (n + 63) // 64, with_coeff=True)
     out_rows = DeviceOp.alloc(No * Ni, (n + 63) // 64, with_coeff=False)
     lib = _lib.lib()
+    # the path of the calls with coefficients: the phase-byte stream serves a power-of-two number of chunks per row (n = 300 is 5 chunks: word-major)
+    if not env:
+        path = WORD_MAJOR if n == 300 else PHASE_STREAM
+    else:
+        path = WIDE if env.get('SYMGPU_WIDE') == '1' else WORD_MAJOR
     try:
         for o0, o1 in ((0, No), (4, 7), (8, 9)):
-            _lib.check(lib.symgpu_mul_allpairs_dev(A.handle, B.handle, o0, o1, 1, out.handle))
+            counted(lambda: _lib.check(lib.symgpu_mul_allpairs_dev(A.handle, B.handle, o0, o1, 1, out.handle)), path, (n, Ni, o0, o1))
             assert out.n_terms == (o1 - o0) * Ni
             rows, coeff = out.download()
             er, ec = oc.mul_allpairs(a, ca, b[o0:o1], cb[o0:o1], True)
             assert np.array_equal(rows, er) and np.array_equal(coeff, ec), (o0, o1)
-            _lib.check(lib.symgpu_mul_allpairs_dev(A.handle, B.handle, o0, o1, 1, out_rows.handle))
+            counted(lambda: _lib.check(lib.symgpu_mul_allpairs_dev(A.handle, B.handle, o0, o1, 1, out_rows.handle)), ROWS_ONLY, (n, Ni, o0, o1, 'rows only'))
             assert out_rows.n_terms == (o1 - o0) * Ni
             assert np.array_equal(out_rows.download(with_coeff=False), er), (o0, o1, 'rows only')
     finally:
