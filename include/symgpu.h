@@ -298,6 +298,27 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
 int symgpu_noncontextual_dev(symgpu_op_t op, int *is_noncontextual);
 int symgpu_state_inner_dev(symgpu_op_t a, symgpu_op_t b, double *out);
 
+/* ---- f3, batched: every term of <phi|H|psi> in one call (PauliwordOp.expval / single_term_expval, base.py:796-819, 2438-2471;
+ * csrc/expval.hip).  For term k of op with symplectic row (x, z) and Y count y = |x & z|
+ *   <phi|P_k|psi> = i^y  sum over b in supp psi with b ^ x in supp phi of  conj(phi[b ^ x]) psi[b] (-1)^{|z & b|}
+ * phi and psi are CLEANED state operators (results of a cleanup, with coefficients, the Wq of op; SYMGPU_E_INVALID otherwise); only their
+ * X halves (the basis strings) and coefficients enter the sums, the Z halves (~X below n, zero above) only the hash.  phi == psi (the same
+ * handle) is the expectation value and builds one table.  op needs coefficients and is NOT cleaned: a repeated term has its own entry.
+ *   out_terms (may be NULL) double [T][2]: <phi|P_k|psi> as (re, im), without the term's coefficient
+ *   out_total double [2]: 0 + c_0 e_0 + c_1 e_1 + ..., plain IEEE complex products added in term order by one wavefront
+ * T = 0 or a state without terms: zeros, *form = 0.  Fewer than 2^31 basis states per state.
+ * Summation order (every run and both forms give the same bits): the states of psi in chunks of C = max(64, the power of two at or above
+ * S_psi / 64) consecutive rows; within a chunk the products conj(phi) psi, negated where |z & b| is odd, are added to 0 in row order;
+ * the chunk sums are added to 0 in ascending order; then i^y as a component swap.
+ * *form (may be NULL) = SYMGPU_EXPVAL_LDS: the look-up table over phi's rows, phi's coefficients and X halves were staged into LDS once per
+ * workgroup, taken when  S_phi (16 + 8 Wq) + 4 cap <= 65536,  cap = the power of two at or above max(64, 2 S_phi)  (Wq = 1: S_phi <= 2048);
+ * or SYMGPU_EXPVAL_GLOBAL: they stayed in memory.  SYMGPU_EXPVAL_FORM=global (read on every call) forces the second form.
+ * Every device scratch buffer is freed before the call returns, also on failure; one read-back, at the end. */
+#define SYMGPU_EXPVAL_LDS 1
+#define SYMGPU_EXPVAL_GLOBAL 2
+int symgpu_expval_terms_dev(symgpu_op_t op, symgpu_op_t phi, symgpu_op_t psi, double *out_terms /* [T][2] or NULL */, double *out_total /* [2] */,
+                            int *form /* or NULL */);
+
 /* ---- f5: PauliwordOp.to_sparse_matrix (base.py:1458-1507) of a resident operator, n_qubits 1 .. 31, as CSR (csrc/sparse_matrix.hip) -------
  * Entry (b, b ^ x_k) = sum over terms k, in operator order, of c_k (-i)^{Y_k} (-1)^{|b & z_k|}; qubit 0 is the MOST significant bit of
  * b and of x_k, z_k.  Duplicate terms are summed, the operator is not cleaned first; entries whose two components are both +-0 are not

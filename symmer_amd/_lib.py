@@ -102,6 +102,7 @@ SIGNATURES = {
     'symgpu_project_dev': [P, P, c_int, P, P, c_int, c_int, c_dbl, c_int, PP, P],
     'symgpu_noncontextual_dev': [P, P],
     'symgpu_state_inner_dev': [P, P, P],
+    'symgpu_expval_terms_dev': [P, P, P, P, P, P],
     'symgpu_to_csr_count': [P, c_int, P, P, PP],
     'symgpu_to_csr_fill': [P, P, P, P, c_int],
     'symgpu_from_matrix_dense': [P, c_int, P, P, c_i64, PP, P, P, P],

@@ -515,6 +515,21 @@ def state_inner_dev(a, b):
     return complex(out[0], out[1])
 
 
+EXPVAL_LDS, EXPVAL_GLOBAL = 1, 2             # SYMGPU_EXPVAL_LDS / SYMGPU_EXPVAL_GLOBAL: where the look-up table of a call lived
+
+
+def expval_terms_dev(op, phi, psi, want_terms=True):
+    """``<phi|P_k|psi>`` for every term of the device operator ``op`` in one call (csrc/expval.hip): ``phi`` and ``psi`` are CLEANED device
+    states (``phi is psi``: the expectation value), ``op`` is taken as it is.  Returns (terms complex128[T] without the terms' coefficients
+    — None with ``want_terms=False`` —, total = sum of c_k * terms[k] in term order, the form that ran)."""
+    t = op.n_terms
+    terms = np.zeros(t, dtype=np.complex128) if want_terms else None
+    total = np.zeros(2, dtype=np.float64)
+    form = c_int(0)
+    check(_lib.lib().symgpu_expval_terms_dev(op.handle, phi.handle, psi.handle, addr(terms), addr(total), ctypes.addressof(form)))
+    return terms, complex(total[0], total[1]), form.value
+
+
 def _host_available_bytes():
     """MemAvailable of /proc/meminfo (None where there is no such file)."""
     try:

@@ -551,12 +551,13 @@ class PauliwordOp:
         return out
 
     def expval(self, psi) -> complex:
-        """base.py:796-819: <psi|H|psi>; many-term operators use one bra x op x ket product, otherwise term by term."""
-        from .quantum_state import single_term_expval
+        """base.py:796-819: <psi|H|psi>; many-term operators use one bra x op x ket product, otherwise the reference goes term by term
+        (a process pool over ``single_term_expval``): here all terms in one device call (csrc/expval.hip), which also forms
+        sum_k c_k <psi|P_k|psi> in term order."""
+        from .quantum_state import _expval_call
         if self.n_terms > psi.n_terms and psi.n_terms > 10:
             return (psi.dagger * self * psi).real
-        expvals = np.array([single_term_expval(P, psi) for P in self]) if self.n_terms > 1 else np.array(single_term_expval(self, psi))
-        return np.sum(expvals * self._c()).real
+        return np.float64(_expval_call(self, psi, False)[1].real)
 
     def __rmul__(self, const):
         if isinstance(const, Number):

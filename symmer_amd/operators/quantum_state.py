@@ -185,3 +185,21 @@ def single_term_expval(P_op, psi: QuantumState) -> float:
     proj = np.vstack([np.zeros(P_op.n_qubits * 2, dtype=bool), P_op.symp_matrix])
     norm_ev = lambda ev: np.linalg.norm((PauliwordOp(proj, [.5, .5 * ev]) * psi).state_op.coeff_vec)
     return (norm_ev(+1) ** 2 - norm_ev(-1) ** 2).real
+
+
+def _expval_call(P_op, psi: QuantumState, want_terms: bool):
+    """One device call for all terms of ``P_op`` (csrc/expval.hip): psi is cleaned on the device, as bra * ket cleans its operands."""
+    from .. import kernels
+    assert P_op.n_qubits == psi.n_qubits, 'operator and state defined for different number of qubits'
+    cleaned = kernels.cleanup_dev(psi.state_op._device())
+    try:
+        return kernels.expval_terms_dev(P_op._device(), cleaned, cleaned, want_terms)
+    finally:
+        cleaned.free()
+
+
+def term_expvals(P_op, psi: QuantumState) -> np.ndarray:
+    """``single_term_expval`` of every term of ``P_op`` at once (the terms' coefficients are ignored), float64[n_terms]:
+    <psi|P_k|psi> = Re i^Y sum_b conj(psi[b ^ x_k]) psi[b] (-1)^|z_k & b|, one table look-up per (term, basis state) instead of
+    two operator x state products per term."""
+    return _expval_call(P_op, psi, True)[0].real.copy()
