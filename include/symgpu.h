@@ -114,6 +114,24 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * word-major coefficient kernel, then rows / the same beside the rows on a second stream.  tests/test_gpu_pair_flows.py and
  * tests/test_gpu_product_coeff_stage.py assert through them which flow and path a call took. */
 int symgpu_debug_counter(int which, int64_t *value);
+/* The radix sort and the two scans that everything else stands on, run directly on device buffers of the caller's (symgpu_dev_alloc /
+ * symgpu_dev_upload), for tests/test_gpu_sort.py.  All three return after a stream synchronisation.
+ *  debug_sort       sorts keys[0..n) (and vals[0..n) with them, if not NULL) in place by key bits [begin_bit, end_bit) (a multiple of 8
+ *                   wide), stable.  form 0: one launch per step of every pass; 1: all passes in one launch if the keys fit it (up to 2^19),
+ *                   else as 0; 2: one launch where the library's thresholds choose it (up to 48 tiles of 4,096 keys, 32 with values), else
+ *                   as 0.  with_first_hist != 0: the entry forms the tile histograms of the first pass itself and hands them in, as a caller
+ *                   does whose own kernel reads the keys anyway; the sort then takes a launch per step whatever `form` says.
+ *                   *form_ran = 1 if the one launch ran, 0 if the launches per step.  If the one launch gave up at a barrier (its
+ *                   workgroups were not co-resident) the call returns SYMGPU_E_HIP, the buffers hold no sorted data, and the form is off
+ *                   for the rest of the process (symgpu_degraded).
+ *  debug_scan       out[i] = in[0] + .. + in[i - 1] (mod 2^32) for i < n, *total (may be NULL; device) = the sum of all; out may equal in.
+ *                   SYMGPU_SCAN_RECURSIVE=1 forces the form of inputs over 2^23 elements.
+ *  debug_popc_scan  out[w] = set bits in words [0, w) of a bitmap of 1 .. 8,192 64-bit words, *total (may be NULL; device) = all of them, in
+ *                   one launch.  n32 = -1, or the number of 32-bit words the bitmap was written in (2 n_words or 2 n_words - 1): if odd, the
+ *                   upper half of the last 64-bit word is unwritten and is not counted. */
+int symgpu_debug_sort(uint64_t *keys, uint32_t *vals, int64_t n, int begin_bit, int end_bit, int form, int with_first_hist, int *form_ran);
+int symgpu_debug_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *total);
+int symgpu_debug_popc_scan(const uint64_t *bits, int64_t n_words, int64_t n32, uint32_t *out, uint32_t *total);
 /* Fast paths that gave up in this process and were replaced by a slower, equally exact form — the one-launch rotation, the one-launch
  * radix sort, the fused selector launch of the GF(2) elimination: their in-kernel waits assume co-resident workgroups and are bounded, so
  * a shared or partitioned GPU turns them off.  Each is announced once on stderr; this returns the list ("" = nothing degraded). */

@@ -44,6 +44,9 @@ SIGNATURES = {
     'symgpu_prof_enable': [c_int, c_int],
     'symgpu_prof_read': [c_int, P, P],
     'symgpu_debug_counter': [c_int, P],
+    'symgpu_debug_sort': [P, P, c_i64, c_int, c_int, c_int, c_int, P],
+    'symgpu_debug_scan': [P, P, c_i64, P],
+    'symgpu_debug_popc_scan': [P, c_i64, c_i64, P, P],
     'symgpu_debug_rotation_trace': [P, c_int, P],
     'symgpu_degraded': [P, c_int],
     'symgpu_membw_probe': [c_i64, P, P],

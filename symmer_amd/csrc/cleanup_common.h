@@ -8,6 +8,7 @@
 //   cleanup_driver.hip    switches, plan, attempt loop, C ABI
 #pragma once
 #include "common.h"
+#include "sort.h"
 
 namespace symgpu {
 
@@ -133,14 +134,12 @@ struct CleanupRun {
     EmitPrefix pre;
     struct Attempt {
         u32 *first_hist = nullptr;   // the first sort pass's histograms, formed by k_mark_singles
-        bool in_tmp = false;         // the sorted keys are in keys2 / idx2
         // what the stages after the sort see: `Tsort` keys ordered by their top `fix_bits` bits — all Tk keys, or (sus_active) only
         // the keys that the flag pass flagged
         i64 Tsort = 0;
         int fix_bits = 64;
-        u64 *ks_sorted = nullptr;
-        bool sus_active = false, sus_coop = false;
-        u64 *ks = nullptr;
+        bool sus_active = false, sus_coop = false;   // sus_coop: the attempt's last sort was the one launch (its give-up flag is read back)
+        u64 *ks = nullptr;           // the sorted keys (in keys or keys2) and, unpacked, their indices (in idx or idx2)
         u32 *is = nullptr;
         bool mark_zeroed = false, merges_found = false, patch_zeroed = false;   // lazy: dirtybits already filled by the fix-up passes
         bool lazy = false;           // the plan's lazy flow, unless the segment sums gave it up

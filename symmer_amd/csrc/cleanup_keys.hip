@@ -619,8 +619,9 @@ static int order_flagged(CleanupRun &r) {
     bump_counter(direct ? 37 : 38);                        // which flag pass this attempt launches: symgpu_debug_counter 37 / 38
     if (!direct) {
         if (pl.key_bytes) SG_TRY(pair_keys(r, false));     // (the flag pass was refused: keys after all)
-        SG_TRY(radix_sort_keys_u64(r.keys.as<u64>(), r.keys2.as<u64>(), Tk, lo, hi, &a.in_tmp, a.first_hist));
-        part = a.in_tmp ? r.keys2.as<u64>() : r.keys.as<u64>(); spare = a.in_tmp ? r.keys.as<u64>() : r.keys2.as<u64>();
+        SortResult res;
+        SG_TRY(radix_sort({part, spare, nullptr, nullptr, Tk, lo, hi, a.first_hist, SortForm::Launches}, &res));
+        part = res.keys; spare = res.spare_keys;
         hipLaunchKernelGGL(k_find_suspects, dim3((unsigned)((Tk + SUS_TILE - 1) / SUS_TILE)), dim3(64 * SUS_WAVES), 0, st, part, Tk, pl.L, r.hI.as<u64>(),
                            r.hO_p, susbits.as<u64>(), sustotal + 1);
     }
@@ -653,15 +654,16 @@ static int order_flagged(CleanupRun &r) {
         bump_counter(44);                                  // symgpu_debug_counter 44: the sort finished on the whole array
         // repeated rows all over: the last pass on the whole array after all (LSD: the order so far is its first passes; the
         // direct flag pass left the keys in index order: all passes)
-        bool in_tmp2 = false;
         if (pl.key_bytes && direct) SG_TRY(pair_keys(r, false));   // (only bytes so far: the keys after all)
-        SG_TRY(radix_sort_keys_u64(part, spare, Tk, direct ? lo : hi, 64, &in_tmp2, direct ? a.first_hist : nullptr));
-        if (in_tmp2) a.in_tmp = !a.in_tmp;
+        SortResult res;
+        SG_TRY(radix_sort({part, spare, nullptr, nullptr, Tk, direct ? lo : hi, 64, direct ? a.first_hist : nullptr, SortForm::Launches}, &res));
+        a.ks = res.keys;
         return SYMGPU_OK;
     }
     bump_counter(45);                                      // symgpu_debug_counter 45: the flagged keys sorted alone (none flagged: nothing to sort)
     a.sus_active = true;
     a.Tsort = h_sus;
+    a.ks = part;
     if (a.Tsort == 0) return SYMGPU_OK;
     // the flagged keys, sorted completely (the same rule for the number of sorted bits, now for a few thousand keys);
     // `part` is not needed any more and serves as the sort's second buffer
@@ -669,35 +671,26 @@ static int order_flagged(CleanupRun &r) {
     // the compaction kept the array order, i.e. the flagged keys are ordered by key bits [lo, hi) already: when the bits to
     // order start inside that range only the passes above it are left (LSD: stable passes on more significant bits)
     const int sort_from = (!direct && 64 - a.fix_bits >= lo && 64 - a.fix_bits < hi) ? hi : 64 - a.fix_bits;
-    bool in_tmp_s = false, coop_done = false;
-    SG_TRY(radix_sort_keys_u64_coop(spare, part, a.Tsort, sort_from, 64, &in_tmp_s, &coop_done));
-    a.sus_coop = coop_done;
-    if (!coop_done) SG_TRY(radix_sort_keys_u64(spare, part, a.Tsort, sort_from, 64, &in_tmp_s));
-    a.ks_sorted = in_tmp_s ? part : spare;
+    SortResult res;
+    SG_TRY(radix_sort({spare, part, nullptr, nullptr, a.Tsort, sort_from, 64, nullptr, SortForm::OneLaunchIfFits}, &res));
+    a.sus_coop = res.one_launch;
+    a.ks = res.keys;
     return SYMGPU_OK;
 }
 
 // the keys (and, unpacked, their indices) in sorted order: r.a.ks / r.a.is
 int cleanup_order(CleanupRun &r) {
     const CleanupPlan &pl = r.pl; CleanupRun::Attempt &a = r.a; const i64 Tk = pl.Tk;
-    if (!pl.packed) {
-        // (plain cleanups of up to 1.3e5 rows: the index sort in ONE launch — its three passes were nine launches, launch bound)
-        bool coop_done = false;
-        SG_TRY(radix_sort_pairs_u64_u32_coop(r.keys.as<u64>(), r.idx.as<u32>(), r.keys2.as<u64>(), r.idx2.as<u32>(), Tk, 64 - pl.nbits, 64, &a.in_tmp, &coop_done));
-        if (coop_done) a.sus_coop = true;
-        else SG_TRY(radix_sort_pairs_u64_u32(r.keys.as<u64>(), r.idx.as<u32>(), r.keys2.as<u64>(), r.idx2.as<u32>(), Tk, 64 - pl.nbits, 64, &a.in_tmp));
-    } else if (!pl.sus_try) {
-        // (small products — up to 2e5 keys, no first-pass histograms at hand —: the sort in ONE launch; its passes were three launches each)
-        bump_counter(36);                                  // symgpu_debug_counter 36: the complete sort of the packed keys, no flag pass
-        bool coop_done = false;
-        if (!a.first_hist) SG_TRY(radix_sort_keys_u64_small(r.keys.as<u64>(), r.keys2.as<u64>(), Tk, 64 - pl.nbits, 64, &a.in_tmp, &coop_done));
-        if (coop_done) a.sus_coop = true;
-        else SG_TRY(radix_sort_keys_u64(r.keys.as<u64>(), r.keys2.as<u64>(), Tk, 64 - pl.nbits, 64, &a.in_tmp, a.first_hist));
-    } else {
-        SG_TRY(order_flagged(r));
-    }
-    a.ks = a.ks_sorted ? a.ks_sorted : (a.in_tmp ? r.keys2.as<u64>() : r.keys.as<u64>());
-    a.is = pl.packed ? nullptr : (a.in_tmp ? r.idx2.as<u32>() : r.idx.as<u32>());
+    if (pl.sus_try) return order_flagged(r);
+    // (plain cleanups of up to 1.3e5 rows: the index sort in ONE launch — its three passes were nine launches, launch bound;
+    // small products — up to 2e5 keys, no first-pass histograms at hand —: the sort in ONE launch; its passes were three launches each)
+    if (pl.packed) bump_counter(36);                       // symgpu_debug_counter 36: the complete sort of the packed keys, no flag pass
+    SortResult res;
+    SG_TRY(radix_sort({r.keys.as<u64>(), r.keys2.as<u64>(), pl.packed ? nullptr : r.idx.as<u32>(), pl.packed ? nullptr : r.idx2.as<u32>(), Tk, 64 - pl.nbits, 64,
+                       a.first_hist, SortForm::OneLaunchWherePays}, &res));
+    a.sus_coop = res.one_launch;
+    a.ks = res.keys;
+    a.is = res.vals;
     return SYMGPU_OK;
 }
 

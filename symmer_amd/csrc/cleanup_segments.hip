@@ -1,6 +1,7 @@
 // cleanup_segments.hip — the segment stages of a cleanup attempt (cleanup_driver.hip): the fix-up of the runs the truncated sort left
 // unordered, the identity segment of a squared operator, and the segment sums with their exact row-against-row verification.
 #include "cleanup_common.h"
+#include "block_scan.h"
 
 namespace symgpu {
 
@@ -451,12 +452,7 @@ __global__ __launch_bounds__(256) void k_fixup_work(u64 *__restrict__ keys, u32 
     const i64 cw = ((i64)blockIdx.x * 4 + wave) * 64 + lane;                  // this lane's chunk: 64 chunks = 4,096 positions per wavefront
     u64 bits = cw < n_chunks ? rarebits[cw] : 0ULL;
     const u32 cnt = (u32)__popcll(bits);
-    u32 incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
+    const u32 incl = wave_incl_scan(cnt, lane);
     const u32 n = __shfl(incl, 63);
     if (n == 0) return;                                                       // wave-uniform
     {

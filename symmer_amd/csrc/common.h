@@ -81,6 +81,15 @@ struct ResidentState {
     u64 *trace = nullptr;          // [RES_MAX_WG][16] phase stamps of the last traced launch (SYMGPU_RES_TRACE=1) and its workgroups
     int trace_wgs = 0;
 };
+// What the scans and the radix sort (scan.hip, sort.hip, sort_coop.hip) keep on a device between calls; allocated on first use,
+// released by sort_state_release (sort.h).
+struct SortState {
+    u32 *scan_ticket = nullptr;    // "last workgroup finishes the scan" tickets, zero between launches: [0] column scan of the sort, [1] exclusive scan
+    u32 *coop_state = nullptr;     // one-launch sort: [0] barrier counter (monotonic over the launches; cleared before it can wrap), [1] time-out
+                                   // flag, [64 ..] tile histograms
+    u32 bar_base = 0;              // value of the barrier counter when the next launch starts
+    bool coop_disabled = false;    // a barrier timed out once (workgroups not co-resident): the process keeps to a launch per step
+};
 struct Context {
     ContextLock lock;
     bool ready = false;
@@ -106,14 +115,11 @@ struct Context {
     u32 *rot_flags = nullptr;      // device u32[4]: [0] = generation in which a duplicate input row was seen
     void *rot_host_cnt = nullptr, *rot_host_cnt_dev = nullptr;   // pinned host copy of a rotation's counts and its device address (rotate_analyze.hip)
     ResidentState res;             // one-launch rotation (rotate_resident.hip)
-    u32 *sort_state = nullptr;     // one-launch radix sort (sort.hip): barrier counter, time-out flag, tile histograms
-    u32 sort_bar_base = 0;
-    bool sort_coop_disabled = false;
+    SortState sort;                // scans and radix sort (sort.h)
     EmitProbe emit_probe[8];          // fused output stage of the cleanup: the output blocks whose block order is being / has been measured (cleanup.hip emit_order_begin)
     u64 emit_stamp = 0;
     u32 *m7_flags = nullptr;       // stream-K commutation kernel (commute_m4r7.hip): per-workgroup words compared with the launch's epoch
     u32 m7_epoch = 0;
-    u32 *sort_scan_ticket = nullptr;   // radix sort: "last workgroup finishes the scan" ticket, zero between launches
 };
 // internal names shared by context.hip, alloc.hip, transfer.hip and op_handles.hip only: kept out of the library's dynamic symbols
 #define SG_HIDDEN __attribute__((visibility("hidden")))
@@ -253,26 +259,6 @@ int read_back_words(const u32 *a, int n_a, const u32 *b, int n_b, u32 *host_out,
 struct ReadBack { int n; u32 seq; u32 plain[8]; };
 int read_back_post(const u32 *a, int n_a, const u32 *b, int n_b, ReadBack *rb, const u32 *c1 = nullptr /* one more word */);   // ... more work may be queued before the wait
 int read_back_wait(ReadBack *rb, u32 *host_out);
-
-// sort.hip
-int exclusive_scan_u32(const u32 *in, u32 *out, i64 n, u32 *total_dev /* may be null: device u32 */);
-// bitmaps of up to POPC_SCAN_SMALL_MAX 64-bit words: out[w] = set bits in the words before w, *total_dev = all of them, one launch (n32: see sort.hip)
-constexpr i64 POPC_SCAN_SMALL_MAX = (i64)1 << 13;
-int popc_scan_small(const u64 *bits, i64 n, i64 n32, u32 *out, u32 *total_dev);
-// first_hist (optional, device, 256 * ceil(n / SORT_TILE) u32): the TILE-major ([tile][256]) tile histograms of the FIRST pass
-// (hist[tile * 256 + digit] = keys of tile `tile` whose bits [begin_bit, begin_bit + 8) equal `digit`), formed by a kernel of the
-// caller's that reads the keys anyway; the buffer then serves the later passes
-constexpr int SORT_TILE = 4096;
-int radix_sort_pairs_u64_u32(u64 *keys, u32 *vals, u64 *keys_tmp, u32 *vals_tmp, i64 n, int begin_bit, int end_bit,
-                             bool *result_in_tmp, u32 *first_hist = nullptr);
-int radix_sort_keys_u64(u64 *keys, u64 *keys_tmp, i64 n, int begin_bit, int end_bit, bool *result_in_tmp, u32 *first_hist = nullptr);
-// the same as one persistent launch (up to 2^19 keys); *done = false: not applicable, use the multi-launch form
-int radix_sort_keys_u64_coop(u64 *keys, u64 *keys_tmp, i64 n, int begin_bit, int end_bit, bool *result_in_tmp, bool *done);
-int radix_sort_keys_u64_small(u64 *keys, u64 *keys_tmp, i64 n, int begin_bit, int end_bit, bool *result_in_tmp, bool *done);   // the one launch where it pays (<= ~2e5 keys)
-int radix_sort_pairs_u64_u32_coop(u64 *keys, u32 *vals, u64 *keys_tmp, u32 *vals_tmp, i64 n, int begin_bit, int end_bit, bool *result_in_tmp, bool *done);
-const u32 *radix_sort_coop_flag();
-void radix_sort_coop_note(u32 flag, bool *timed_out);
-int radix_sort_coop_check(bool *timed_out);     // after a stream synchronisation: did a one-launch sort give up (output invalid)?
 
 // commute_driver.hip (what the commutation files share among themselves: commute_common.h)
 // b_owner (may be null): the operator B's rows belong to (all of them), so that per-operand layouts can be cached on it

@@ -1,5 +1,6 @@
 // context.hip — error text, the per-device contexts and their lock (DeviceScope), init / shutdown, timers, profiling, debug counters.
 #include "common.h"
+#include "sort.h"
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -262,8 +263,7 @@ static void shutdown_device(int device) {
     if (c.hash_tab) { (void)hipFree(c.hash_tab); c.hash_tab = nullptr; }
     if (c.xs_pow) { (void)hipFree(c.xs_pow); c.xs_pow = nullptr; }
     if (c.rot_flags) { (void)hipFree(c.rot_flags); c.rot_flags = nullptr; }
-    if (c.sort_state) { (void)hipFree(c.sort_state); c.sort_state = nullptr; c.sort_bar_base = 0; }
-    if (c.sort_scan_ticket) { (void)hipFree(c.sort_scan_ticket); c.sort_scan_ticket = nullptr; }
+    sort_state_release(c.sort);
     if (c.m7_flags) { (void)hipFree(c.m7_flags); c.m7_flags = nullptr; }
     for (auto &q : c.emit_probe) {
         for (auto &ev : q.ev) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }

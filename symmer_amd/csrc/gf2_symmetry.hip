@@ -1,6 +1,7 @@
 // gf2_symmetry.hip — the symmetry-generator kernel (IndependentOp.symmetry_generators, symmer/operators/independent_op.py:124-126):
 // build the stacked matrix on the device, reduce it (rref_dev, gf2.hip) and read the generators out.
 #include "common.h"
+#include "sort.h"
 
 namespace symgpu {
 

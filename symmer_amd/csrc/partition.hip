@@ -9,6 +9,7 @@
 // threshold — the result carries the pair index of each term's first occurrence again, so the same call (without cleanup) puts the
 // all-gathered shares of all ranks into the reference's order (utils.py:271).  Nothing leaves the device.
 #include "common.h"
+#include "sort.h"
 #include <stdlib.h>
 #include <vector>
 
@@ -157,11 +158,11 @@ int symgpu_merge_indexed_dev(const symgpu_op_t *parts, int n_parts, int key_bits
     }
     if (e != hipSuccess) { symgpu_op_free(sorted); return hip_fail(e, "merge_indexed_dev: concatenation", __FILE__, __LINE__); }
     hipLaunchKernelGGL(k_iota_u32, dim3(grid_of(total)), dim3(256), 0, st, pos.as<u32>(), total);
-    bool in_tmp = false;
-    rc = radix_sort_pairs_u64_u32(keys.as<u64>(), pos.as<u32>(), keys2.as<u64>(), pos2.as<u32>(), total, 0, sort_bits, &in_tmp);
+    SortResult by_first;
+    rc = radix_sort({keys.as<u64>(), keys2.as<u64>(), pos.as<u32>(), pos2.as<u32>(), total, 0, sort_bits, nullptr, SortForm::Launches}, &by_first);
     if (rc != SYMGPU_OK) { symgpu_op_free(sorted); return rc; }
-    const u64 *ks = in_tmp ? keys2.as<u64>() : keys.as<u64>();
-    const u32 *ps = in_tmp ? pos2.as<u32>() : pos.as<u32>();
+    const u64 *ks = by_first.keys;
+    const u32 *ps = by_first.vals;
     hipLaunchKernelGGL(k_gather_rows_u32, dim3(grid_of(total * Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(cat_rows.p), cat_coeff.as<double>(), ps, total, Wq,
                        reinterpret_cast<u32x4 *>(sorted->rows), sorted->coeff);
     e = hipGetLastError();

@@ -17,6 +17,8 @@
 //      = ascending (x, z) into a new operator.  Basis: c(x_k, z_k) for the K terms in basis order, zeros included.
 // Every form performs the same additions in the same order: all results are bit-reproducible.
 #include "common.h"
+#include "sort.h"
+#include "block_scan.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
@@ -270,28 +272,18 @@ __global__ __launch_bounds__(256) void k_pd_emit(PdSlots P, const u32 *__restric
     __shared__ u32 s_wave[4];
     const u64 base = (u64)blockIdx.x * PD_SEL;
     u64 out = excl[blockIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int j = 0; j < PD_SEL / 256; ++j) {
         u64 x = 0, z = 0;
         f64x2 c = {0.0, 0.0};
         const bool keep = pd_slot_value(P, base + j * 256 + threadIdx.x, &x, &z, &c);
-        const u64 ballot = __ballot(keep);
-        const u32 before = __builtin_amdgcn_mbcnt_hi((u32)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((u32)ballot, 0u));
-        if (lane == 0) s_wave[wave] = (u32)__popcll(ballot);
-        __syncthreads();
-        u32 wbase = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            wbase += w < wave ? s_wave[w] : 0u;
-            all += s_wave[w];
-        }
-        const u64 pos = out + wbase + before;
+        u32 all;
+        const u64 pos = out + block_compact_256(keep, s_wave, &all);
         if (keep && pos < T) {
             rows[2 * pos] = __brevll(x) >> (64 - P.n);
             rows[2 * pos + 1] = __brevll(z) >> (64 - P.n);
             coeff[pos] = c;
         }
         out += all;
-        __syncthreads();
     }
 }
 
@@ -547,9 +539,9 @@ static int pd_csr(const double *data, const IDX *indices, const IDX *indptr, i64
         hipLaunchKernelGGL(k_pd_csr_keys<IDX>, dim3(pd_grid(nnz)), dim3(256), 0, st, d_idx.as<IDX>(), d_ptr.as<IDX>(), nnz, n, key.as<u64>(),
                            row_of.as<u32>(), flags.as<u32>());
         KERNEL_CHECK();
-        bool in_tmp = false;
-        SG_TRY(radix_sort_keys_u64(key.as<u64>(), key_tmp.as<u64>(), nnz, 0, (n + 7) / 8 * 8, &in_tmp));
-        const u64 *sorted = in_tmp ? key_tmp.as<u64>() : key.as<u64>();
+        SortResult by_x;
+        SG_TRY(radix_sort({key.as<u64>(), key_tmp.as<u64>(), nullptr, nullptr, nnz, 0, (n + 7) / 8 * 8, nullptr, SortForm::Launches}, &by_x));
+        const u64 *sorted = by_x.keys;
         if (basis.K > 0) {
             SG_TRY(bxs.alloc(basis.xs.size() * 8));
             HIP_TRY(hipMemcpyAsync(bxs.p, basis.xs.data(), basis.xs.size() * 8, hipMemcpyHostToDevice, st));

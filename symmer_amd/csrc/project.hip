@@ -9,6 +9,7 @@
 //   symgpu_state_inner_dev    QuantumState bra * ket (base.py:1808-1815): a hash join of the packed basis rows of two cleaned states,
 //                             products added in the left state's order (the reference's Python loop order).
 #include "common.h"
+#include "sort.h"
 #include <string.h>
 #include "rotate_common.h"
 #include <stdlib.h>

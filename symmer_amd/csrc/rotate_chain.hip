@@ -22,6 +22,7 @@
 // rows of a power-of-two number of 16-byte chunks (<= 32); SYMGPU_CHAIN_REG=0 keeps the multi-launch forms (the tests run both).
 #include "common.h"
 #include "rotate_common.h"
+#include "sort.h"
 #include <stdlib.h>
 
 namespace symgpu {
@@ -229,12 +230,11 @@ static int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u
         });
         delete prof;
         KERNEL_CHECK();
-        bool in_tmp = false, coop = false;
         const int end_bit = CHAIN_IDX_BITS + 8 * ((n + 7) / 8);
-        SG_TRY(radix_sort_keys_u64_coop(knew, ktmp, T, CHAIN_IDX_BITS, end_bit, &in_tmp, &coop));     // one launch for all passes up to 2^19 keys
-        if (!coop) SG_TRY(radix_sort_keys_u64(knew, ktmp, T, CHAIN_IDX_BITS, end_bit, &in_tmp));
-        bump_counter(coop ? 27 : 28);                                               // (a run that is redone after a time-out counts both)
-        perm = in_tmp ? ktmp : knew;
+        SortResult sorted;
+        SG_TRY(radix_sort({knew, ktmp, nullptr, nullptr, T, CHAIN_IDX_BITS, end_bit, nullptr, SortForm::OneLaunchIfFits}, &sorted));     // one launch for all passes up to 2^19 keys
+        bump_counter(sorted.one_launch ? 27 : 28);                                  // (a run that is redone after a time-out counts both)
+        perm = sorted.keys;
         symgpu_op_t t2 = cur; cur = other; other = t2;
     }
     if (perm) {

@@ -2,6 +2,7 @@
 // the register chain (rotate_chain.hip): LDS-resident and single-workgroup kernels for small operators, two launches per rotation, and
 // the Clifford fast path's four launches per rotation.  Every form returns with the stream synchronised.
 #include "rotate_common.h"
+#include "block_scan.h"
 
 namespace symgpu {
 
@@ -63,8 +64,7 @@ __global__ __launch_bounds__(1024) void k_clifford_chain(u64 *__restrict__ rowsA
         u32 mine = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) { const int t = 8 * (int)threadIdx.x + j; if (t < T) mine += s_anti[t]; }
-        u32 incl = mine;
-        for (int off = 1; off < 64; off <<= 1) { const u32 v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+        const u32 incl = wave_incl_scan(mine, lane);
         if (lane == 63) s_wsum[wave] = incl;
         __syncthreads();
         if (threadIdx.x == 0) { u32 acc = 0; for (int w2 = 0; w2 < 16; ++w2) { const u32 v = s_wsum[w2]; s_wsum[w2] = acc; acc += v; } s_total = acc; }

@@ -1,6 +1,7 @@
 // rotate_general.hip — the general rotation path (what operators with duplicate rows take, and every rotation under
 // SYMGPU_ROTATE_GENERAL): the reference's stacked operator (base.py:1139-1161) built row by row, then the cleanup that merges duplicates.
 #include "rotate_common.h"
+#include "sort.h"
 
 namespace symgpu {
 

@@ -13,6 +13,8 @@
 //      RB * D slots do not fit, or SYMGPU_CSR_SCRATCH=1); the slots, read in [row][rank] order, ARE the CSR order, so one block scan
 //      per 256 slots compacts them into coalesced writes of data / indices.
 #include "common.h"
+#include "sort.h"
+#include "block_scan.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(CSR_WG) void k_csr_fill(CsrTerms P, int RB, u64 blo
     const u64 rows_here = rows - row0 < (u64)RB ? rows - row0 : (u64)RB;
     const size_t S_valid = (size_t)rows_here * D;
     u64 out = indptr[row0];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    static_assert(CSR_WG == 256, "block_compact_256");
     for (size_t base = 0; base < S_valid; base += CSR_WG) {
         const size_t i = base + threadIdx.x;
         f64x2 v = {0.0, 0.0};
@@ -197,23 +199,13 @@ __global__ __launch_bounds__(CSR_WG) void k_csr_fill(CsrTerms P, int RB, u64 blo
             col = sc[i];
             keep = csr_kept(v);
         }
-        const u64 ballot = __ballot(keep);
-        const u32 before = __builtin_amdgcn_mbcnt_hi((u32)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((u32)ballot, 0u));
-        if (lane == 0) s_wave[wave] = (u32)__popcll(ballot);
-        __syncthreads();
-        u32 wbase = 0, total = 0;
-        for (int w = 0; w < CSR_WG / 64; ++w) {
-            const u32 c = s_wave[w];
-            wbase += w < wave ? c : 0u;
-            total += c;
-        }
-        const u64 pos = out + wbase + before;
+        u32 total;
+        const u64 pos = out + block_compact_256(keep, s_wave, &total);
         if (keep && pos < nnz) {
             data[pos] = v;
             indices[pos] = (IDX)col;
         }
         out += total;
-        __syncthreads();
     }
 }
 
@@ -331,10 +323,10 @@ static int csr_count(symgpu_op_t op, int n, symgpu_csr_s *p) {
         SG_TRY(gexcl.alloc((size_t)T * 4 + 4));
         hipLaunchKernelGGL(k_csr_keys, dim3(csr_grid(T)), dim3(256), 0, st, op->rows, T, n, key.as<u64>(), idx.as<u32>());
         KERNEL_CHECK();
-        bool in_tmp = false;
-        SG_TRY(radix_sort_pairs_u64_u32(key.as<u64>(), idx.as<u32>(), key_tmp.as<u64>(), idx_tmp.as<u32>(), T, 0, (n + 7) / 8 * 8, &in_tmp));
-        const u64 *k = in_tmp ? key_tmp.as<u64>() : key.as<u64>();
-        const u32 *ix = in_tmp ? idx_tmp.as<u32>() : idx.as<u32>();
+        SortResult by_x;
+        SG_TRY(radix_sort({key.as<u64>(), key_tmp.as<u64>(), idx.as<u32>(), idx_tmp.as<u32>(), T, 0, (n + 7) / 8 * 8, nullptr, SortForm::Launches}, &by_x));
+        const u64 *k = by_x.keys;
+        const u32 *ix = by_x.vals;
         hipLaunchKernelGGL(k_csr_heads, dim3(csr_grid(T)), dim3(256), 0, st, k, T, head.as<u32>());
         KERNEL_CHECK();
         u32 *d_total = gexcl.as<u32>() + T;
