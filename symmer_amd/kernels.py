@@ -85,6 +85,16 @@ class DeviceOp:
     def set_rows(self, t):
         check(_lib.lib().symgpu_op_set_rows(self.handle, int(t)))
 
+    def copy_rows_from(self, src, src_begin, n, at=0):
+        """Rows [src_begin, src_begin + n) of ``src`` to rows [at, at + n) of this operator (a peer copy when the devices differ).  The
+        row count stays as it is (``set_rows``)."""
+        if n:
+            check(_lib.lib().symgpu_op_copy_rows(self.handle, int(at), src.handle, int(src_begin), int(n)))
+
+    def write(self, at, rows, coeff, n):
+        """``n`` host rows (and their coefficients, or None) to rows [at, at + n); the row count stays as it is."""
+        check(_lib.lib().symgpu_op_write(self.handle, int(at), addr(rows), addr(coeff), int(n)))
+
     def download(self, with_coeff=True):
         t, wq, _ = self.info()
         rows = np.empty((t, 2 * wq), dtype='<u8')
@@ -136,6 +146,13 @@ class DeviceOp:
             _lib.load().symgpu_op_free(self.handle)
         self.handle = None
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
     def __del__(self):
         try:
             self.free()
@@ -144,24 +161,24 @@ class DeviceOp:
 
 
 def concat_dev(parts, with_coeff=True):
-    """Device operators stacked in order into a new one (device-to-device copies)."""
+    """Device operators (on any devices) stacked in order into a new one on the current device (device-to-device copies)."""
     sizes = [p.info() for p in parts]
     wq = sizes[0][1]
-    out = DeviceOp.alloc(sum(t for t, _, _ in sizes), wq, with_coeff)
+    total = sum(t for t, _, _ in sizes)
+    out = DeviceOp.alloc(max(1, total), wq, with_coeff)
     at = 0
     for p, (t, w, _) in zip(parts, sizes):
         assert w == wq, 'operands packed with different Wq'
-        if t:
-            check(_lib.lib().symgpu_op_copy_rows(out.handle, at, p.handle, 0, t))
+        out.copy_rows_from(p, 0, t, at)
         at += t
+    out.set_rows(total)
     return out
 
 
 def slice_dev(op, begin, end, with_coeff=True):
     """Rows [begin, end) of a device operator as a new one."""
     out = DeviceOp.alloc(end - begin, op.info()[1], with_coeff)
-    if end > begin:
-        check(_lib.lib().symgpu_op_copy_rows(out.handle, 0, op.handle, int(begin), int(end - begin)))
+    out.copy_rows_from(op, begin, end - begin)
     return out
 
 
@@ -251,14 +268,8 @@ def cleanup(rows, coeff, zero_threshold=1e-15):
     assert rows.shape[0] == coeff.shape[0]
     if rows.shape[0] == 0:
         return rows.copy(), coeff.copy()
-    thr, use = _thr_args(zero_threshold)
-    op = DeviceOp.upload(rows, coeff)
-    out = ctypes.c_void_p()
-    try:
-        check(_lib.lib().symgpu_cleanup_dev(op.handle, thr, use, ctypes.byref(out)))
-        return DeviceOp(out).download()
-    finally:
-        op.free()
+    with DeviceOp.upload(rows, coeff) as op, cleanup_dev(op, zero_threshold) as res:
+        return res.download()
 
 
 MAX_PAIRS_PER_CALL = 1 << 31      # one device call sorts 32-bit pair indices; larger products are tiled over the outer operand
@@ -278,19 +289,19 @@ def mul_cleanup_handles(a, b, inner_is_left=True, zero_threshold=1e-15, max_pair
         return DeviceOp(out)
     slab = max(1, max_pairs // ni)
     parts = []
-    for o0 in range(0, no, slab):
-        piece = slice_dev(b, o0, min(no, o0 + slab))
-        part = ctypes.c_void_p()
-        # partial sums must not be thresholded: a term may only cancel across slabs
-        check(_lib.lib().symgpu_mul_cleanup_dev(a.handle, piece.handle, 1 if inner_is_left else 0, 0.0, 0, ctypes.byref(part)))
-        piece.free()
-        parts.append(DeviceOp(part))
-    stacked = concat_dev(parts)
-    for p in parts:
-        p.free()
-    check(_lib.lib().symgpu_cleanup_dev(stacked.handle, thr, use, ctypes.byref(out)))
-    stacked.free()
-    return DeviceOp(out)
+    try:
+        for o0 in range(0, no, slab):
+            part = ctypes.c_void_p()
+            with slice_dev(b, o0, min(no, o0 + slab)) as piece:
+                # partial sums must not be thresholded: a term may only cancel across slabs
+                check(_lib.lib().symgpu_mul_cleanup_dev(a.handle, piece.handle, 1 if inner_is_left else 0, 0.0, 0, ctypes.byref(part)))
+            parts.append(DeviceOp(part))
+        stacked = concat_dev(parts)
+    finally:
+        for p in parts:                                            # gone before the final cleanup takes its workspace
+            p.free()
+    with stacked:
+        return cleanup_dev(stacked, zero_threshold)
 
 
 def mul_cleanup(inner, ci, outer, co, inner_is_left=True, zero_threshold=1e-15, max_pairs=None):
@@ -301,18 +312,9 @@ def mul_cleanup(inner, ci, outer, co, inner_is_left=True, zero_threshold=1e-15, 
     assert inner.shape[1] == outer.shape[1]
     if inner.shape[0] == 0 or outer.shape[0] == 0:
         return np.empty((0, inner.shape[1]), dtype='<u8'), np.empty(0, dtype=np.complex128)
-    a = DeviceOp.upload(inner, ci)
-    b = a if same else DeviceOp.upload(outer, co)
-    try:
-        res = mul_cleanup_handles(a, b, inner_is_left, zero_threshold, max_pairs)
-        try:
-            return res.download()
-        finally:
-            res.free()
-    finally:
-        a.free()
-        if b is not a:
-            b.free()
+    with DeviceOp.upload(inner, ci) as a, (a if same else DeviceOp.upload(outer, co)) as b, \
+            mul_cleanup_handles(a, b, inner_is_left, zero_threshold, max_pairs) as res:
+        return res.download()
 
 
 import functools
@@ -634,7 +636,7 @@ def pauli_decompose_csr(data, indices, indptr, n_qubits, basis_x=None, basis_z=N
                        n_qubits, bx, bz, K)
 
 
-# ---- cleanups that also return the first-occurrence index of every output term (hash-partitioned multi-GPU cleanup, parallel.py) ----
+# ---- cleanups that also return the first-occurrence index of every output term (hash-partitioned multi-GPU cleanup, sharding.py) ----
 def _first_index(op):
     t = op.n_terms
     first = np.zeros(t, dtype='<u8')
@@ -649,18 +651,9 @@ def mul_cleanup_indexed(inner, ci, outer, co, inner_is_left=True, zero_threshold
     if inner.shape[0] == 0 or outer.shape[0] == 0:
         z = np.zeros(0, dtype=np.int64)
         return np.empty((0, inner.shape[1]), dtype='<u8'), np.empty(0, dtype=np.complex128), z, z
-    thr, use = _thr_args(zero_threshold)
-    a = DeviceOp.upload(inner, ci)
-    b = DeviceOp.upload(outer, co)
-    out = ctypes.c_void_p()
-    try:
-        check(_lib.lib().symgpu_mul_cleanup_indexed_dev(a.handle, b.handle, 1 if inner_is_left else 0, thr, use, ctypes.byref(out)))
-        res = DeviceOp(out)
+    with DeviceOp.upload(inner, ci) as a, DeviceOp.upload(outer, co) as b, mul_cleanup_indexed_dev(a, b, inner_is_left, zero_threshold) as res:
         rows, coeff = res.download()
         first = _first_index(res)
-        res.free()
-    finally:
-        a.free(); b.free()
     return rows, coeff, (first & 0xFFFFFFFF).astype(np.int64), (first >> 32).astype(np.int64)
 
 
@@ -670,16 +663,12 @@ def cleanup_indexed(rows, coeff, zero_threshold=1e-15):
     if rows.shape[0] == 0:
         return rows.copy(), coeff.copy(), np.zeros(0, dtype=np.int64)
     thr, use = _thr_args(zero_threshold)
-    op = DeviceOp.upload(rows, coeff)
     out = ctypes.c_void_p()
-    try:
+    with DeviceOp.upload(rows, coeff) as op:
         check(_lib.lib().symgpu_cleanup_indexed_dev(op.handle, thr, use, ctypes.byref(out)))
-        res = DeviceOp(out)
-        r, c = res.download()
-        first = _first_index(res).astype(np.int64)
-        res.free()
-    finally:
-        op.free()
+        with DeviceOp(out) as res:
+            r, c = res.download()
+            first = _first_index(res).astype(np.int64)
     return r, c, first
 
 

@@ -9,7 +9,7 @@ sharded is what SURVEY §8e / BASELINE's north star shard:
   (``symgpu_comm_allgather_ops``), every device computes its ``[N / G, M]`` block, and the blocks come back to the host in parallel (one
   PCIe link per device: the 40 GB result of cfg5 is the whole cost of the API call on one GPU).
 * the product + cleanup behind ``__mul__`` (base.py:821-859): the OUTER index in contiguous blocks — pair ``(i, o)`` has index ``o * Ni + i``
-  in the reference, so device-major order is the reference's order (``parallel.Communicator.mul_cleanup_sharded`` explains why that makes
+  in the reference, so device-major order is the reference's order (``sharding.sharded_mul_cleanup_dev`` explains why that makes
   the result identical): a fused product + cleanup per device without threshold, the cleaned parts copied to device 0 (peer copies),
   one cleanup of their concatenation with the threshold.
 
@@ -23,7 +23,7 @@ import ctypes
 import os
 import threading
 import numpy as np
-from . import _lib, packing
+from . import _lib, kernels, packing
 from .parallel import shard_bounds
 
 
@@ -33,7 +33,6 @@ class HipBackend:
     ``ncclCommInitAll``.  If RCCL cannot be brought up the right operand is staged through the host instead (``degraded`` says so)."""
 
     def __init__(self, n_devices):
-        from . import kernels
         self.k = kernels
         self.lib = _lib.load()
         _lib.check(self.lib.symgpu_init_all(int(n_devices)))
@@ -66,14 +65,13 @@ class HipBackend:
         self.use(d)
         wq = (source.info()[1] if isinstance(source, self.k.DeviceOp) else source[0].shape[1] // 2)
         op = self.k.DeviceOp.alloc(max(1, capacity), wq, with_coeff)
-        if r1 > r0:
-            if isinstance(source, self.k.DeviceOp):
-                _lib.check(self.lib.symgpu_op_copy_rows(op.handle, 0, source.handle, int(r0), int(r1 - r0)))     # peer copy when the devices differ
-            else:
-                rows, coeff = source
-                rows = np.ascontiguousarray(rows[r0:r1], dtype='<u8')
-                c = None if (coeff is None or not with_coeff) else np.ascontiguousarray(coeff[r0:r1], dtype=np.complex128)
-                _lib.check(self.lib.symgpu_op_write(op.handle, 0, rows.ctypes.data, None if c is None else c.ctypes.data, int(r1 - r0)))
+        if isinstance(source, self.k.DeviceOp):
+            op.copy_rows_from(source, r0, r1 - r0)                  # peer copy when the devices differ
+        elif r1 > r0:
+            rows, coeff = source
+            rows = np.ascontiguousarray(rows[r0:r1], dtype='<u8')
+            c = None if (coeff is None or not with_coeff) else np.ascontiguousarray(coeff[r0:r1], dtype=np.complex128)
+            op.write(0, rows, c, r1 - r0)
         op.set_rows(r1 - r0)
         return op
 
@@ -91,9 +89,7 @@ class HipBackend:
             ts = shards[0].info()[2]
             for d, f in enumerate(fulls):
                 for s_idx, s in enumerate(shards):
-                    t = s.info()[0]
-                    if t:
-                        _lib.check(self.lib.symgpu_op_copy_rows(f.handle, s_idx * ts, s.handle, 0, t))
+                    f.copy_rows_from(s, 0, s.info()[0], s_idx * ts)
                 f.set_rows(ts * self.n)
         for f in fulls:
             f.set_rows(n_rows_total)
@@ -146,15 +142,7 @@ class HipBackend:
     def concat_on(self, d, parts):
         """The operators (on any devices) stacked in order on device d."""
         self.use(d)
-        sizes = [p.info() for p in parts]
-        out = self.k.DeviceOp.alloc(max(1, sum(t for t, _, _ in sizes)), sizes[0][1], True)
-        at = 0
-        for p, (t, _, _) in zip(parts, sizes):
-            if t:
-                _lib.check(self.lib.symgpu_op_copy_rows(out.handle, at, p.handle, 0, t))
-            at += t
-        out.set_rows(at)
-        return out
+        return self.k.concat_dev(parts)
 
     def cleanup(self, d, op, zero_threshold):
         self.use(d)

@@ -6,7 +6,7 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from symmer_amd import _lib, kernels, parallel
+from symmer_amd import _lib, kernels, parallel, sharding
 from symmer_amd.kernels import DeviceOp
 from oracle import oracle_c as oc
 
@@ -53,7 +53,7 @@ a2 = (rng.integers(-8, 9, Ni2) + 1j * rng.integers(-8, 9, Ni2)) / 16.0; b2 = (rn
 _, ob = parallel.shard_bounds(No2, world)
 inner = DeviceOp.upload(A2, a2)
 outer = DeviceOp.upload(B2[ob[rank][0]:ob[rank][1]], b2[ob[rank][0]:ob[rank][1]])
-res = comm.mul_cleanup_sharded(inner, outer, True, 1e-15)
+res = sharding.sharded_mul_cleanup_dev(comm, inner, outer, True, 1e-15)
 rr, rc = res.download()
 er, ec = oc.mul(A2, a2, B2, b2)
 assert np.array_equal(rr, er) and np.array_equal(rc, ec), 'sharded product + cleanup differs from the oracle'
@@ -64,7 +64,7 @@ for h in (inner, outer, res):
 innerf = DeviceOp.upload(A2, a2); outerf = DeviceOp.upload(B2, b2)
 for X, Y, ex in ((innerf, outerf, (A2, a2, B2, b2)), (innerf, innerf, (A2, a2, A2, a2))):
     st = {}
-    res = comm.mul_cleanup_hash_partitioned(X, Y, True, 1e-15, stats=st)
+    res = sharding.hash_partitioned_mul_cleanup_dev(comm, X, Y, True, 1e-15, stats=st)
     rr, rc = res.download()
     pr, pc = oc.mul_allpairs(*ex, True)
     er, ec = oc.cleanup(pr, pc, 1e-15)

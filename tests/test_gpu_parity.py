@@ -880,10 +880,10 @@ def test_quantum_state_golden(case):
 
 def test_indexed_cleanups_and_hash_partitioned_shares():
     """The cleanups that return first-occurrence indices (symgpu_*_indexed_dev) against the oracle, and the hash-partitioned multi-GPU cleanup
-    (parallel.hash_partition_local) with the DEVICE kernels: the shares of G = 1, 2, 3, 4, 8 ranks, computed one after the other on this GPU
+    (sharding.hash_partition_local) with the DEVICE kernels: the shares of G = 1, 2, 3, 4, 8 ranks, computed one after the other on this GPU
     and merged by first pair index, equal the single-process oracle result — squared operators (twins on one rank), general products in both
     operand orders, repeated rows, through and below the size gates of the lazy cleanup flow."""
-    from symmer_amd import parallel
+    from symmer_amd import sharding
     rng = np.random.default_rng(606)
     for n, Ni, No in ((100, 700, 400), (1000, 2100, 2100), (40, 300, 5)):
         A = onp.pack_rows(rng.random((Ni, 2 * n)) < 0.3); B = onp.pack_rows(rng.random((No, 2 * n)) < 0.3)
@@ -913,7 +913,7 @@ def test_indexed_cleanups_and_hash_partitioned_shares():
                 shares, owned = [], 0
                 for rank in range(G):
                     st = {}
-                    shares.append(parallel.hash_partition_local(X, x, Y, y, rank, G, left, 1e-15, stats=st))
+                    shares.append(sharding.hash_partition_local(X, x, Y, y, rank, G, left, 1e-15, stats=st))
                     owned += st['pairs_owned']
                     assert st['keys_exchanged'] == 0
                 assert owned == X.shape[0] * Y.shape[0], 'every pair has exactly one owner'
@@ -928,7 +928,7 @@ def test_hash_partitioned_shares_device_resident():
     """The device-resident share computation (csrc/partition.hip: gather of sub-operands, indexed fused product + cleanup, pair indices, merge by
     index) for G = 1, 2, 3, 8: the shares merged by pair index on the device (symgpu_merge_indexed_dev without cleanup) are the oracle's result,
     also above the 2^22-key gate of the lazy cleanup flow (squared 3,000-term operator) and with Gaussian coefficients within 1e-12."""
-    from symmer_amd import parallel
+    from symmer_amd import sharding
     from symmer_amd.kernels import DeviceOp
     rng = np.random.default_rng(707)
     for n, Ni, No, gauss in ((100, 700, 400, False), (1000, 900, 900, False), (100, 3000, 3000, False), (70, 500, 300, True)):
@@ -947,7 +947,7 @@ def test_hash_partitioned_shares_device_resident():
                 # G = 1 and 2 of the first case also with the sub-products CUT along their outer index (the limit of one indexed product call is
                 # 2^32 pairs — at the north star's 1e5 x 1e5 terms and two classes a sub-product has 2.5e9 .. 5e9): forced here with a tiny limit
                 cut = 9000 if (G <= 2 and Ni == 700) else None
-                shares = [parallel.hash_partition_local_dev(X, Y, rank, G, left, 1e-15, max_pairs=cut) for rank in range(G)]
+                shares = [sharding.hash_partition_local_dev(X, Y, rank, G, left, 1e-15, max_pairs=cut) for rank in range(G)]
                 key_bits = int(ex[0].shape[0] * ex[2].shape[0] - 1).bit_length()
                 merged = kernels.merge_indexed_dev(shares, key_bits, False)
                 rows, coeff = merged.download()

@@ -196,10 +196,10 @@ def test_circuit_rotation_string_last_write_wins_and_negative_indices():
 
 
 def test_hash_partition_classes_are_linear_and_shares_partition_the_product():
-    """symmer_amd/parallel.py, hash-partitioned multi-GPU cleanup (no GPU: checker kernels built on the oracle): the row class is GF(2)-linear
+    """symmer_amd/sharding.py, hash-partitioned multi-GPU cleanup (no GPU: checker kernels built on the oracle): the row class is GF(2)-linear
     (class of a product row = XOR of the operands' classes), every pair has exactly one owner for any world size, and the shares of
     G = 1 .. 8 ranks merged by first pair index are the single-process result — rows, order and sums (dyadic: bit for bit)."""
-    from symmer_amd import parallel
+    from symmer_amd import sharding
     from oracle import oracle_c as oc, oracle_np as onp
     rng = np.random.default_rng(11)
     n, Ni, No = 70, 90, 57
@@ -207,9 +207,9 @@ def test_hash_partition_classes_are_linear_and_shares_partition_the_product():
     A[40:50] = A[:10]; B[30:35] = B[:5]
     a = (rng.integers(-8, 9, Ni) + 1j * rng.integers(-8, 9, Ni)) / 16.0; b = (rng.integers(-8, 9, No) + 1j * rng.integers(-8, 9, No)) / 16.0
     for bits in (1, 3, 5):
-        ca, cb = parallel.linear_row_classes(A, bits), parallel.linear_row_classes(B, bits)
+        ca, cb = sharding.linear_row_classes(A, bits), sharding.linear_row_classes(B, bits)
         prod = (A[:, None, :] ^ B[None, :, :]).reshape(-1, A.shape[1])
-        assert np.array_equal(parallel.linear_row_classes(prod, bits), (ca[:, None] ^ cb[None, :]).ravel())
+        assert np.array_equal(sharding.linear_row_classes(prod, bits), (ca[:, None] ^ cb[None, :]).ravel())
         assert ca.max() < (1 << bits)
 
     def indexed_cleanup(r, c, thr):
@@ -230,7 +230,7 @@ def test_hash_partition_classes_are_linear_and_shares_partition_the_product():
             shares, owned = [], 0
             for rank in range(G):
                 st = {}
-                shares.append(parallel.hash_partition_local(X, x, Y, y, rank, G, left, 1e-15, indexed_mul, indexed_cleanup, st))
+                shares.append(sharding.hash_partition_local(X, x, Y, y, rank, G, left, 1e-15, indexed_mul, indexed_cleanup, st))
                 owned += st['pairs_owned']
             assert owned == X.shape[0] * Y.shape[0]
             g = np.concatenate([s[2] for s in shares])

@@ -1,4 +1,5 @@
-"""CPU, world_size 2 over gloo: the left-axis sharding + right-operand all-gather logic of symmer_amd/parallel.py.
+"""CPU, world_size 2 over gloo and over TCP: the left-axis sharding + right-operand all-gather logic of symmer_amd/parallel.py and
+symmer_amd/sharding.py.
 The per-rank kernel is injected (the C oracle stands in for the HIP kernel, which needs a GPU), so this checks
 exactly the multi-rank plumbing: shard bounds, padded gather, block placement."""
 import os, socket, sys
@@ -13,28 +14,30 @@ def _free_port():
     s = socket.socket(); s.bind(('127.0.0.1', 0)); p = s.getsockname()[1]; s.close(); return p
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, control):
     try:
         sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
         os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
-        from symmer_amd import parallel
+        from symmer_amd import parallel, sharding
         from oracle import oracle_c as oc, oracle_np as onp
-        comm = parallel.Communicator.from_env(data_plane='gloo-host', control='gloo')
+        comm = parallel.Communicator.from_env(data_plane='gloo-host', control=control)
         rng = np.random.default_rng(77)                       # same global operands on every rank
         n, N, M = 130, 37, 51
         A = onp.pack_rows(rng.random((N, 2 * n)) < 0.3); B = onp.pack_rows(rng.random((M, 2 * n)) < 0.3)
         a = (rng.integers(-8, 9, N) + 1j * rng.integers(-8, 9, N)) / 16.0; b = (rng.integers(-8, 9, M) + 1j * rng.integers(-8, 9, M)) / 16.0
         ts, bounds = parallel.shard_bounds(M, world)
         m0, m1 = bounds[rank]
-        (r0, r1), blk = parallel.sharded_commutes(A, B[m0:m1], M, comm, kernel=oc.commutes)
+        (r0, r1), blk = sharding.sharded_commutes(A, B[m0:m1], M, comm, kernel=oc.commutes)
         full = oc.commutes(A, B)
         ok = np.array_equal(blk, full[r0:r1]) and (r0, r1) == parallel.shard_bounds(N, world)[1][rank]
-        (r0, r1), rows, coeff = parallel.sharded_product(A, a, B[m0:m1], b[m0:m1], M, comm, kernel=oc.mul_allpairs)
+        (r0, r1), rows, coeff = sharding.sharded_product(A, a, B[m0:m1], b[m0:m1], M, comm, kernel=oc.mul_allpairs)
         erows, ecoeff = oc.mul_allpairs(A[r0:r1], a[r0:r1], B, b, True)
         ok = ok and np.array_equal(rows, erows) and np.array_equal(coeff, ecoeff)
         t = comm.max_over_ranks(float(rank + 1))
         ok = ok and t == float(world)
         comm.close()
+        if control == 'tcp':
+            ok = ok and 'torch' not in sys.modules                # bench.py's plane: no PyTorch in the process
         q.put((rank, bool(ok), ''))
     except Exception as e:                                    # pragma: no cover
         import traceback
@@ -54,11 +57,12 @@ def test_shard_bounds():
 
 
 @pytest.mark.timeout(300)
-def test_world_size_2_gloo():
+@pytest.mark.parametrize('control', ['gloo', 'tcp'])
+def test_world_size_2_gloo(control):
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, control)) for r in range(2)]
     for p in procs:
         p.start()
     res = [q.get(timeout=240) for _ in procs]
@@ -68,13 +72,30 @@ def test_world_size_2_gloo():
         assert ok, f'rank {rank} failed: {err}'
 
 
+def test_communicator_without_environment_has_a_control_plane():
+    """World 1, built directly (no environment): every control-plane call is the identity, without sockets and without torch (another
+    test of this process may have imported torch before: these calls must not be what brings it in)."""
+    from symmer_amd import parallel
+    torch_before = 'torch' in sys.modules
+    comm = parallel.Communicator()
+    assert comm.control.allgather(b'abc') == b'abc'
+    assert comm.control.bcast(b'x', 1) == b'x'
+    assert comm.max_over_ranks(2.5) == 2.5
+    assert comm.barrier() is None
+    x = np.arange(18, dtype='<u8').reshape(3, 6)
+    got = comm.allgather_rows_host(x, 3)
+    assert got.dtype == x.dtype and got.shape == x.shape and np.array_equal(got, x)
+    assert comm.close() is None
+    assert ('torch' in sys.modules) == torch_before
+
+
 def _tcp_worker(rank, world, port, q):
     try:
         sys.path.insert(0, ROOT)
         os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
         from symmer_amd import parallel
         comm = parallel.Communicator.from_env(data_plane='none', control='tcp')     # bench.py's control plane, no torch
-        payload = comm._bcast_bytes(bytes(range(128)), 128)
+        payload = comm.control.bcast(bytes(range(128)), 128)
         ok = payload == bytes(range(128)) and comm.max_over_ranks(10.0 * (rank + 1)) == 10.0 * world
         comm.barrier()
         comm.close()
@@ -159,7 +180,7 @@ def _rccl_fallback_worker(rank, world, port, q, disable_on):
         comm = parallel.Communicator.from_env(data_plane='rccl', control='tcp')
         ok = comm.gathers and bool(comm.rccl_error) and comm.data_plane == 'host-staged' and bool(comm.degraded) and not calls
         # the fallback's transport: equal-sized byte strings, concatenated in rank order on every rank
-        got = comm._allgather_bytes(bytes([rank + 1]) * 5000)
+        got = comm.control.allgather(bytes([rank + 1]) * 5000)
         ok = ok and got == b''.join(bytes([r + 1]) * 5000 for r in range(world))
         comm.barrier()
         comm.close()
@@ -214,7 +235,7 @@ def _first_gather_worker(rank, world, port, q, mode):
         elif mode == 'error':
             ok = outcome == 'returned' and comm.data_plane == 'host-staged' and bool(comm.degraded) and 'all-gather failed' in comm.degraded
             # the fallback's transport still works on both ranks
-            got = comm._allgather_bytes(bytes([rank + 7]) * 100)
+            got = comm.control.allgather(bytes([rank + 7]) * 100)
             ok = ok and got == b''.join(bytes([r + 7]) * 100 for r in range(world))
         else:
             ok = outcome.startswith('hang:')                       # on BOTH ranks, although the gather returned on rank 0
@@ -261,7 +282,7 @@ def _mul_cleanup_worker(rank, world, port, q):
     try:
         sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
         os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
-        from symmer_amd import parallel
+        from symmer_amd import parallel, sharding
         from oracle import oracle_c as oc, oracle_np as onp
         comm = parallel.Communicator.from_env(data_plane='gloo-host', control='gloo')
         ok = True
@@ -278,7 +299,7 @@ def _mul_cleanup_worker(rank, world, port, q):
             def mul_kernel(inner, ci, outer, co, left, thr):
                 r, c = oc.mul_allpairs(inner, ci, outer, co, left) if outer.shape[0] else (np.zeros((0, inner.shape[1]), dtype='<u8'), np.zeros(0, dtype=complex))
                 return oc.cleanup(r, c, thr) if r.shape[0] else (r, c)
-            rows, coeff = parallel.sharded_mul_cleanup(A, a, B[m0:m1], b[m0:m1], comm, True, 1e-15, mul_kernel=mul_kernel,
+            rows, coeff = sharding.sharded_mul_cleanup(A, a, B[m0:m1], b[m0:m1], comm, True, 1e-15, mul_kernel=mul_kernel,
                                                        cleanup_kernel=lambda r, c, thr: oc.cleanup(r, c, thr))
             er, ec = oc.mul(A, a, B, b)
             ok = ok and np.array_equal(rows, er) and np.array_equal(coeff, ec)
@@ -298,14 +319,14 @@ def _mul_cleanup_worker(rank, world, port, q):
                 return rr, cc, first % inner.shape[0], first // inner.shape[0]
             for (X, x, Y, y, left) in ((A, a, B, b, True), (A, a, A, a, True), (B, b, A, a, False)):
                 st = {}
-                rows, coeff = parallel.hash_partitioned_mul_cleanup(X, x, Y, y, comm, left, 1e-15, mul_kernel=indexed_mul, cleanup_kernel=indexed_cleanup, stats=st)
+                rows, coeff = sharding.hash_partitioned_mul_cleanup(X, x, Y, y, comm, left, 1e-15, mul_kernel=indexed_mul, cleanup_kernel=indexed_cleanup, stats=st)
                 rr, cc = oc.mul_allpairs(X, x, Y, y, left)
                 er, ec = oc.cleanup(rr, cc, 1e-15)
                 ok = ok and np.array_equal(rows, er) and np.array_equal(coeff, ec)
                 # every pair has exactly one owner, and what a rank sends is its share of the RESULT — no key, no partial product row
-                owned = np.frombuffer(comm._allgather_bytes(np.int64(st['pairs_owned']).tobytes()), dtype=np.int64)
+                owned = np.frombuffer(comm.control.allgather(np.int64(st['pairs_owned']).tobytes()), dtype=np.int64)
                 ok = ok and int(owned.sum()) == st['pairs_total'] == X.shape[0] * Y.shape[0]
-                sent = np.frombuffer(comm._allgather_bytes(np.int64(st['bytes_sent']).tobytes()), dtype=np.int64)
+                sent = np.frombuffer(comm.control.allgather(np.int64(st['bytes_sent']).tobytes()), dtype=np.int64)
                 ok = ok and int(sent.sum()) == er.shape[0] * (er.shape[1] * 8 + 16 + 8)
                 # (no key and no partial product is exchanged at all: the bytes a rank sends are exactly its kept terms — row, coefficient,
                 # first pair index — i.e. the result is the only traffic, 1/G of it per rank on average)
