@@ -378,6 +378,40 @@ int symgpu_from_matrix_dense(const double *matrix, int n_qubits, const uint64_t 
 int symgpu_from_matrix_csr(const double *data, const void *indices, const void *indptr, int index_bytes, int64_t nnz, int n_qubits,
                            const uint64_t *basis_x, const uint64_t *basis_z, int64_t K, symgpu_op_t *out, int64_t *n_out, double *coeff_out, int *form);
 
+/* ---- g: measurement grouping (qubitwise_commutes_termwise base.py:985-1009, clique_cover base.py:1266-1364; csrc/clique.hip) ----------
+ * Relations of two packed rows a = (xa | za), b = (xb | zb):
+ *   SYMGPU_REL_C    related iff the parity of popcount(xa & zb ^ za & xb) over the row is even (the terms commute)
+ *   SYMGPU_REL_AC   related iff that parity is odd
+ *   SYMGPU_REL_QWC  related iff no word has (xa | za) & (xb | zb) & ((xa ^ xb) | (za ^ zb)) != 0 (they commute qubit by qubit)
+ * In the degrees and in the colouring a term is never related to (and never conflicts with) itself: itself is the same INDEX, an equal
+ * row at another index is a term like any other.
+ * symgpu_qwc_dev   as symgpu_commutes_dev for QWC: out_dev[i * M + j] = 1 iff A[a_begin + i] qubit-wise commutes with B[j] (np.bool_ layout,
+ *   N * M bytes from symgpu_dev_alloc); a term qubit-wise commutes with itself.
+ * symgpu_relation_degrees_dev   deg_host[t] = the number of terms u != t related to t: an all-pairs pass with integer row sums, 8 T bytes of
+ *   device scratch, no table.
+ * symgpu_clique_colour_dev   first-fit colouring of the CONFLICT graph (terms that are not related) in the order given: for s = 0 .. T-1 term
+ *   order_host[s] takes the lowest colour none of whose members it conflicts with, a new one if there is none.  Every colour class is a
+ *   clique of the relation; this is `sorted_insertion` for order = argsort(-|c|) and networkx's greedy_color(complement, 'largest_first')
+ *   for order = stable argsort of -(T - 1 - degree).  colour_host[t] (by term index) in 0 .. *n_colours - 1, colours opened in order.
+ *   order_host must be a permutation of 0 .. T-1 (checked on the host before the device is touched).  T = 0: nothing is written but
+ *   *n_colours = 0.  Coefficients are not read.
+ *   info (may be NULL) int64 [4]: [0] the form that ran — SYMGPU_CLIQUE_PAIRS (relations C and AC): every term met every term coloured before
+ *   it, T^2 / 2 pair predicates; SYMGPU_CLIQUE_UNIONS (QWC): every term met the merged Pauli string of every clique open before its block,
+ *   T K predicates for K colours — [1] the blocks of the order that were resolved (ceil(T / [2])), [2] the terms a block, [3] the 32-bit words of
+ *   a term's forbidden-colour bitmap (T / 32 + 2: as wide as colours can become).
+ *   Device memory: 16 Wq T bytes (rows in colouring order; as much again for SYMGPU_CLIQUE_UNIONS) + 12 T + 4 (order, colours) +
+ *   256 (T / 32 + 2) 4 (the bitmaps of ONE block) — O(T Wq + T), no T x T table.  Two launches a block, no read-back before the last.
+ * Every device scratch buffer is freed before a call returns, also on failure. */
+#define SYMGPU_REL_C 0
+#define SYMGPU_REL_AC 1
+#define SYMGPU_REL_QWC 2
+#define SYMGPU_CLIQUE_PAIRS 1
+#define SYMGPU_CLIQUE_UNIONS 2
+int symgpu_qwc_dev(symgpu_op_t A, int64_t a_begin, int64_t a_end, symgpu_op_t B, uint8_t *out_dev);
+int symgpu_relation_degrees_dev(symgpu_op_t op, int relation, int64_t *deg_host /* [T] */);
+int symgpu_clique_colour_dev(symgpu_op_t op, int relation, const int64_t *order_host /* [T], a permutation */,
+                             int32_t *colour_host /* [T], by term index */, int64_t *n_colours, int64_t *info /* [4] or NULL */);
+
 /* ---- e: multi-GPU (one process per GPU; RCCL over xGMI) ------------------------------------------- */
 #define SYMGPU_UNIQUE_ID_BYTES 128
 int symgpu_comm_available(void);                                                /* librccl loadable? (no device, no collective) */

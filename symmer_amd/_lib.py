@@ -106,6 +106,9 @@ SIGNATURES = {
     'symgpu_noncontextual_dev': [P, P],
     'symgpu_state_inner_dev': [P, P, P],
     'symgpu_expval_terms_dev': [P, P, P, P, P, P],
+    'symgpu_qwc_dev': [P, c_i64, c_i64, P, P],
+    'symgpu_relation_degrees_dev': [P, c_int, P],
+    'symgpu_clique_colour_dev': [P, c_int, P, P, P, P],
     'symgpu_to_csr_count': [P, c_int, P, P, PP],
     'symgpu_to_csr_fill': [P, P, P, P, c_int],
     'symgpu_from_matrix_dense': [P, c_int, P, P, c_i64, PP, P, P, P],

@@ -245,6 +245,50 @@ def commutes_handles(a, b):
     return out.view(np.bool_)
 
 
+# ---- measurement grouping (csrc/clique.hip) --------------------------------------------------------------------------------------
+REL_C, REL_AC, REL_QWC = 0, 1, 2             # SYMGPU_REL_*: the termwise relations
+RELATIONS = {'C': REL_C, 'AC': REL_AC, 'QWC': REL_QWC}
+CLIQUE_PAIRS, CLIQUE_UNIONS = 1, 2           # SYMGPU_CLIQUE_*: the form of a colouring call
+
+
+def qwc_handles(a, b):
+    """bool[N, M] for two device operators: True where a's term i and b's term j commute qubit by qubit (``symgpu_qwc_dev``); the table is
+    computed into device memory and read back once."""
+    (n, wq, _), (m, wq_b, _) = a.info(), b.info()
+    assert wq == wq_b, 'operands packed with different Wq'
+    out = np.empty((n, m), dtype=np.uint8)
+    if n and m:
+        buf = ctypes.c_void_p()
+        check(_lib.lib().symgpu_dev_alloc(n * m, ctypes.byref(buf)))
+        try:
+            check(_lib.lib().symgpu_qwc_dev(a.handle, 0, n, b.handle, buf))
+            check(_lib.lib().symgpu_dev_download(buf, addr(out), n * m))
+        finally:
+            _lib.lib().symgpu_dev_free(buf)
+    return out.view(np.bool_)
+
+
+def relation_degrees_dev(op, relation):
+    """int64[T]: for every term of the device operator the number of OTHER terms it is related to (``relation``: REL_C / REL_AC / REL_QWC)."""
+    deg = np.zeros(op.n_terms, dtype=np.int64)
+    check(_lib.lib().symgpu_relation_degrees_dev(op.handle, int(relation), addr(deg)))
+    return deg
+
+
+def clique_colouring_dev(op, relation, order, want_info=False):
+    """First-fit colouring of the terms of a device operator in ``order`` (a permutation of its term indices): every term takes the lowest
+    colour all of whose members it is related to (``symgpu_clique_colour_dev``).  Returns (int32 colours[T] by term index, n_colours), with
+    ``want_info`` also the call's info words (form, blocks resolved, terms a block, bitmap words a term)."""
+    order = np.ascontiguousarray(order, dtype=np.int64)
+    t = op.n_terms
+    assert order.shape == (t,), 'order must name every term once'
+    colours = np.zeros(t, dtype=np.int32)
+    n_colours = c_i64(0)
+    info = np.zeros(4, dtype=np.int64)
+    check(_lib.lib().symgpu_clique_colour_dev(op.handle, int(relation), addr(order), addr(colours), ctypes.addressof(n_colours), addr(info)))
+    return (colours, n_colours.value, info) if want_info else (colours, n_colours.value)
+
+
 def mul_allpairs(inner, ci, outer, co, inner_is_left=True):
     """Uncleaned product: row ``o*Ni + i`` = ``inner[i] ^ outer[o]`` with its phase-corrected coefficient."""
     inner, outer, ci, co = _rows(inner), _rows(outer), _coeff(ci), _coeff(co)

@@ -3,7 +3,8 @@
 construction, ``+ - *``, ``cleanup``, commutation/adjacency, single-Pauli rotations and GF(2) generator
 routines, ``to_sparse_matrix`` (a scipy CSR matrix built on the device, csrc/sparse_matrix.hip) and its inverse
 ``from_matrix`` / ``haar_random`` (csrc/pauli_decomp.hip).  The data-parallel work runs in hand-written HIP
-kernels (``libsymgpu.so``); host code is NumPy glue only.  Out of scope (not on the path): graph colouring, openfermion/qiskit converters (SURVEY.md §2, §8f);
+kernels (``libsymgpu.so``); host code is NumPy glue only.  ``clique_cover`` colours on the device for 'sorted_insertion' and
+'largest_first' (csrc/clique.hip); the other networkx strategies stay on the host.  Out of scope (not on the path): openfermion/qiskit converters (SURVEY.md §2, §8f);
 ``QuantumState`` lives in quantum_state.py.
 """
 import warnings
@@ -629,12 +630,15 @@ class PauliwordOp:
 
     # ---- graph glue on the device-computed adjacency matrix (reference base.py:985-1364; networkx, host) ------------
     def qubitwise_commutes_termwise(self, PwordOp: "PauliwordOp") -> np.ndarray:
-        """base.py:985-1009: True where terms commute qubit by qubit (host NumPy; not a hot-path kernel)."""
+        """base.py:985-1009: bool ``[N, M]``, True where terms commute qubit by qubit; one device call on the packed rows (csrc/clique.hip),
+        the table read back once."""
         assert self.n_qubits == PwordOp.n_qubits, 'Pauliwords defined for different number of qubits'
-        xa, za = self.X_block[:, None, :], self.Z_block[:, None, :]
-        xb, zb = PwordOp.X_block[None, :, :], PwordOp.Z_block[None, :, :]
-        both = (xa | za) & (xb | zb)
-        return np.all(~both | ((xa == xb) & (za == zb)), axis=2)
+        if self.n_qubits == 0:
+            return np.ones((self.n_terms, PwordOp.n_terms), dtype=bool)
+        if self.n_terms == 0 or PwordOp.n_terms == 0:
+            return np.empty((self.n_terms, PwordOp.n_terms), dtype=bool)
+        a = self._device(rows_only=True)
+        return kernels.qwc_handles(a, a if PwordOp is self else PwordOp._device(rows_only=True))
 
     @cached_property
     def adjacency_matrix_qwc(self) -> np.ndarray:
@@ -660,9 +664,20 @@ class PauliwordOp:
         pauli_indices = sorted(nx.find_cliques(graph), key=lambda x: -len(x))[0]
         return sum([self[i] for i in pauli_indices])
 
-    def clique_cover(self, edge_relation: str = 'C', strategy: str = 'largest_first', colouring_interchange: bool = False
-                     ) -> Dict[int, "PauliwordOp"]:
-        """base.py:1266-1364: clique partition by greedy colouring of the complement graph, or 'sorted_insertion'."""
+    def clique_cover(self, edge_relation: str = 'C', strategy: str = 'largest_first', colouring_interchange: bool = False,
+                     _host: bool = False) -> Dict[int, "PauliwordOp"]:
+        """base.py:1266-1364: clique partition by greedy colouring of the complement graph, or 'sorted_insertion'.
+
+        'sorted_insertion' and 'largest_first' (without ``colouring_interchange``) are both a first-fit walk over the terms in a fixed
+        order — by decreasing magnitude, or by decreasing degree in the complement graph with ties in index order — and run on the device
+        (csrc/clique.hip): the order from the host, one colouring call, one gather per clique; clique k holds its terms in colouring
+        order, stays resident, and the keys are 0 .. K-1 in that order.  The host path of the reference (a term-by-term loop, or networkx)
+        still serves every other networkx strategy, ``colouring_interchange=True``, 0-qubit operators, and operators with a duplicate row
+        or a coefficient with |c| <= 1e-15: there the reference's per-term ``+`` merges or drops terms and the result is not a plain
+        partition.  ``_host=True`` forces the host path (benchmarks and tests)."""
+        if (not _host and strategy in ('sorted_insertion', 'largest_first') and colouring_interchange is False
+                and edge_relation in kernels.RELATIONS and self.n_qubits > 0 and self.n_terms > 0 and self._is_plain_partition_input()):
+            return self._clique_cover_device(kernels.RELATIONS[edge_relation], strategy)
         if strategy == 'sorted_insertion':
             if colouring_interchange is not False:
                 warnings.warn(f'{strategy} is not a graph colouring method, so colouring_interchange flag is ignored')
@@ -684,6 +699,32 @@ class PauliwordOp:
         cliques = {}
         for p_index, colour in col_map.items():
             cliques[colour] = cliques.get(colour, PauliwordOp.from_list(['I' * self.n_qubits], [0])) + self[p_index]
+        return cliques
+
+    def _is_plain_partition_input(self) -> bool:
+        """No coefficient with |c| <= 1e-15 and no two equal rows (one device cleanup without a threshold counts the distinct rows)."""
+        if np.any(np.abs(self._c()) <= 1e-15):
+            return False
+        with kernels.cleanup_dev(self._device(), None) as merged:
+            return merged.n_terms == self.n_terms
+
+    def _clique_cover_device(self, relation: int, strategy: str) -> Dict[int, "PauliwordOp"]:
+        dev = self._device()
+        if strategy == 'sorted_insertion':
+            order = self._ORDERINGS['magnitude'](self)
+        else:
+            # networkx's largest_first: stable, descending by degree in the complement graph
+            degree = kernels.relation_degrees_dev(dev, relation)
+            order = np.argsort(-(self.n_terms - 1 - degree), kind='stable')
+        colours, n_colours = kernels.clique_colouring_dev(dev, relation, order)
+        in_order = colours[order]
+        by_colour = np.argsort(in_order, kind='stable')               # positions of the order, grouped by colour, colouring order within
+        sizes = np.bincount(in_order, minlength=n_colours)
+        ends = np.cumsum(sizes)
+        cliques = {}
+        for k in range(n_colours):
+            members = order[by_colour[ends[k] - sizes[k]:ends[k]]]
+            cliques[k] = PauliwordOp._from_device(kernels.op_gather(dev, members), self.n_qubits, len(members))
         return cliques
 
     def commutator(self, PwordOp: "PauliwordOp") -> "PauliwordOp":
