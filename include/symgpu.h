@@ -112,7 +112,9 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
  * SYMGPU_CLEANUP_UNPACKED=1, index fields over 32 bits) count none of 36 .. 46.  48 .. 52: calls of symgpu_mul_allpairs_dev (and of
  * symgpu_mul_allpairs) with at least one pair to form (counted before the path runs, whether or not it succeeds), by path: rows only / phase-byte row stream / wide coefficient kernel, then rows /
  * word-major coefficient kernel, then rows / the same beside the rows on a second stream.  tests/test_gpu_pair_flows.py and
- * tests/test_gpu_product_coeff_stage.py assert through them which flow and path a call took. */
+ * tests/test_gpu_product_coeff_stage.py assert through them which flow and path a call took.  53 / 54: launches of the fill kernel of
+ * symgpu_to_csr_fill (k_csr_fill) with its slots in LDS / in global scratch: one per call in LDS, one per chunk of workgroups whose slots
+ * fit the scratch limit otherwise.  tests/test_gpu_csr_families.py asserts through them which form a shape took and in how many launches. */
 int symgpu_debug_counter(int which, int64_t *value);
 /* The radix sort and the two scans that everything else stands on, run directly on device buffers of the caller's (symgpu_dev_alloc /
  * symgpu_dev_upload), for tests/test_gpu_sort.py.  All three return after a stream synchronisation.
@@ -348,7 +350,9 @@ int symgpu_expval_terms_dev(symgpu_op_t op, symgpu_op_t phi, symgpu_op_t psi, do
  * symgpu_to_csr_fill    consumes the plan: data (complex128 [nnz]), indices ([nnz]) and indptr ([2^n + 1]), both of index_bytes = 4
  *   (int32) or 8 (int64), written into host buffers; every device buffer of the plan is freed before it returns, also on failure.
  *   All three buffers NULL: the plan is only freed (a caller that cannot hold the output).  SYMGPU_CSR_SCRATCH=1 forces the fill's
- *   global-scratch form (taken by itself when a row's groups do not fit the LDS). */
+ *   global-scratch form (taken by itself when a row's groups do not fit the LDS).  SYMGPU_CSR_SCRATCH_MIB=m replaces the 512 MiB limit
+ *   of that scratch per launch by m MiB (the floor of four workgroups per compute unit per launch stays): the fill then takes several
+ *   launches at a small size, as it does by itself when the slots of all rows exceed 512 MiB. */
 typedef struct symgpu_csr_s *symgpu_csr_t;
 int symgpu_to_csr_count(symgpu_op_t op, int n_qubits, int64_t *nnz, int64_t *fill_scratch_bytes, symgpu_csr_t *plan);
 int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *indptr, int index_bytes);

@@ -138,7 +138,7 @@ void forget_bound_device();                // after a library (RCCL) may have ch
         if (!(_done.fetch_or(_bit) & _bit) && (expr)) _ok.fetch_or(_bit);                             \
         return (_ok.load() & _bit) != 0;                                                              \
     }())
-extern std::atomic<i64> g_counters[53];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
+extern std::atomic<i64> g_counters[55];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
                                            // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls),
                                            // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
                                            // [14] uses of a context by a call that did not hold its lock, [15] blocks panelled by the blocked GF(2)
@@ -160,7 +160,9 @@ extern std::atomic<i64> g_counters[53];    // debug counters (symgpu_debug_count
                                            // after the flag pass, [45] the flagged keys sorted alone, [46] single terms marked from bytes,
                                            // [47] the attempt repeated with the full 64-bit sort,
                                            // [48] .. [52] calls of symgpu_mul_allpairs_dev by ProductPath: rows only / phase stream / wide coefficients /
-                                           // word-major, then rows / word-major beside rows (product_driver.hip, at the switch)
+                                           // word-major, then rows / word-major beside rows (product_driver.hip, at the switch),
+                                           // [53] / [54] launches of k_csr_fill with its slots in LDS / in global scratch (sparse_matrix.hip
+                                           // csr_fill_launch, nowhere else)
 inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
 inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
 inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }

@@ -10,8 +10,9 @@
 //      fp64 adds with the sign taken from the parity of b & z; counts[b] = kept entries of row b (4 B per row).
 //   3. 64-bit exclusive scan of the counts -> indptr (device).
 //   4. fill pass: the same sums for a block of RB rows; each value lands at [row][rank] of a slot array (LDS, or global scratch when
-//      RB * D slots do not fit, or SYMGPU_CSR_SCRATCH=1); the slots, read in [row][rank] order, ARE the CSR order, so one block scan
-//      per 256 slots compacts them into coalesced writes of data / indices.
+//      RB * D slots do not fit, or SYMGPU_CSR_SCRATCH=1, in several launches once the slots of all rows exceed 512 MiB, or
+//      SYMGPU_CSR_SCRATCH_MIB); the slots, read in [row][rank] order, ARE the CSR order, so one block scan per 256 slots compacts them
+//      into coalesced writes of data / indices.
 #include "common.h"
 #include "sort.h"
 #include "block_scan.h"
@@ -285,6 +286,14 @@ static bool csr_force_scratch() {
     return e && e[0] == '1';
 }
 
+// global slot scratch per launch: CSR_SCRATCH_MAX, or SYMGPU_CSR_SCRATCH_MIB MiB (read per call: the tests make the fill take several
+// launches at a small size, as it does by itself when the slots of all rows exceed the limit)
+static size_t csr_scratch_max() {
+    const char *e = getenv("SYMGPU_CSR_SCRATCH_MIB");
+    const long long m = e ? atoll(e) : 0;
+    return m > 0 && m <= (1 << 20) ? (size_t)m << 20 : CSR_SCRATCH_MAX;
+}
+
 }  // namespace symgpu
 
 using namespace symgpu;
@@ -396,7 +405,7 @@ static CsrFillForm csr_fill_form(const symgpu_csr_s *p) {
     }
     const size_t per_blk = (size_t)CSR_WG * per_row;
     f.nblk = (N + CSR_WG - 1) / CSR_WG;
-    f.chunk = CSR_SCRATCH_MAX / per_blk;
+    f.chunk = csr_scratch_max() / per_blk;
     if (f.chunk < (u64)4 * ctx().num_cu) f.chunk = (u64)4 * ctx().num_cu;   // at least four workgroups per CU in every launch
     if (f.chunk > f.nblk) f.chunk = f.nblk;
     f.scratch_bytes = (size_t)f.chunk * per_blk;
@@ -419,6 +428,7 @@ static int csr_fill_launch(const symgpu_csr_s *p, const CsrFillForm &f, f64x2 *d
             hipLaunchKernelGGL((k_csr_fill<true, IDX>), dim3((unsigned)nb), dim3(CSR_WG), 0, st, P, f.RB, b0, (const u64 *)p->indptr, p->nnz,
                                slots.as<char>(), data, indices);
         KERNEL_CHECK();
+        bump_counter(f.lds ? 53 : 54);                     // symgpu_debug_counter 53 / 54: launches of the fill by form, here and nowhere else
     }
     return SYMGPU_OK;
 }

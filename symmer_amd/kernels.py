@@ -593,18 +593,39 @@ def csr_index_dtype(nnz, n_qubits):
     return np.int32 if max(int(nnz), 1 << int(n_qubits)) <= np.iinfo(np.int32).max else np.int64
 
 
-def to_csr(devop, n_qubits):
+def csr_forced_index_dtype(nnz, n_qubits, index_dtype):
+    """The index dtype of ``to_csr``: ``csr_index_dtype`` for None, else the forced int32 / int64; ValueError for any other dtype and for
+    an int32 that cannot hold ``nnz`` or ``2^n``."""
+    natural = csr_index_dtype(nnz, n_qubits)
+    if index_dtype is None:
+        return natural
+    forced = np.dtype(index_dtype)
+    if forced not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise ValueError(f'to_csr: index_dtype = {index_dtype!r} is neither int32 nor int64')
+    if forced == np.dtype(np.int32) and natural is not np.int32:
+        raise ValueError(f'to_csr: {int(nnz)} entries of a 2^{int(n_qubits)} x 2^{int(n_qubits)} matrix do not fit int32 indices')
+    return forced.type
+
+
+def to_csr(devop, n_qubits, index_dtype=None):
     """``PauliwordOp.to_sparse_matrix`` (base.py:1458-1507) of a device operator of 1 <= n_qubits <= 31 as ``(data, indices, indptr)``
     NumPy arrays of a canonical ``2^n x 2^n`` CSR matrix: entry (b, b ^ x_k) sums ``c_k (-i)^{Y_k} (-1)^{|b & z_k|}`` over the terms in
     operator order, qubit 0 the most significant bit of b; entries whose two components are both +-0 are not stored.  The exact entry
-    count is known before the output is allocated: MemoryError if it does not fit the device or the host."""
+    count is known before the output is allocated: MemoryError if it does not fit the device or the host.  ``index_dtype``: None for
+    the dtype scipy would choose (``csr_index_dtype``), ``np.int32`` / ``np.int64`` to force the width of ``indices`` and ``indptr``
+    (ValueError if int32 is forced and cannot hold the result)."""
     n_qubits = int(n_qubits)
+    csr_forced_index_dtype(0, n_qubits, index_dtype)          # a bad index_dtype is refused before any device work
     if not 1 <= n_qubits <= 31:
         raise ValueError(f'to_csr: n_qubits = {n_qubits} outside 1 .. 31 (column indices must fit an int32 index space)')
     nnz_c, scratch_c, plan = c_i64(0), c_i64(0), ctypes.c_void_p()
     check(_lib.lib().symgpu_to_csr_count(devop.handle, n_qubits, ctypes.addressof(nnz_c), ctypes.addressof(scratch_c), ctypes.byref(plan)))
     nnz, side = int(nnz_c.value), 1 << n_qubits
-    idx_dtype = csr_index_dtype(nnz, n_qubits)
+    try:
+        idx_dtype = csr_forced_index_dtype(nnz, n_qubits, index_dtype)
+    except ValueError:
+        check(_lib.lib().symgpu_to_csr_fill(plan, None, None, None, 4))               # frees the plan
+        raise
     ib = np.dtype(idx_dtype).itemsize
     host_need = nnz * (16 + ib) + (side + 1) * ib
     # what the fill allocates on the device: data + indices, the int32 copy of indptr (the int64 one is already held by the plan, so the

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import scipy.sparse
 
+import _csr_families as fam
 import _pauli_decomp_oracle as po
 from symmer_amd import PauliwordOp, kernels, packing, _lib
 
@@ -422,3 +423,168 @@ def test_c_abi_refuses_broken_csr_arrays():
     dev, t, form = kernels.pauli_decompose_csr(sp.data, sp.indices, sp.indptr, 2)
     assert t == 1 and form == kernels.PAULI_ONE_PASS                 # the same arrays, intact: the identity matrix is the term II
     dev.free()
+
+
+# ---- the families of tests/_csr_families.py: index width, block bases of the dense gather, more than 16 qubits -------------------------
+def _in_both_forms(monkeypatch, n, call):
+    """call() in the one-pass form and with tiles of 8 slots (two-pass above 3 qubits); the forms are asserted."""
+    monkeypatch.delenv('SYMGPU_PAULI_TILE_BITS', raising=False)
+    one = call()
+    monkeypatch.setenv('SYMGPU_PAULI_TILE_BITS', '3')
+    two = call()
+    monkeypatch.delenv('SYMGPU_PAULI_TILE_BITS')
+    assert one[-1] == kernels.PAULI_ONE_PASS and two[-1] == (kernels.PAULI_TWO_PASS if n > 3 else kernels.PAULI_ONE_PASS)
+    return one, two
+
+
+def _terms_of(result):
+    """(packed rows, coefficients, term count) of a (DeviceOp, n_terms, form) result; the handle is freed."""
+    dev, t, _ = result
+    rows, coeff = dev.download()
+    dev.free()
+    assert rows.shape[0] == t == coeff.shape[0]
+    return rows, coeff, t
+
+
+def _packed_of(x, z, n):
+    """uint64[T, 2] of terms given as n-bit integers (qubit 0 the most significant bit): qubit q is bit q of the packed word."""
+    x, z = np.asarray(x, dtype=np.uint64), np.asarray(z, dtype=np.uint64)
+    out = np.zeros((len(x), 2), dtype='<u8')
+    for q in range(n):
+        s = np.uint64(n - 1 - q)
+        out[:, 0] |= ((x >> s) & np.uint64(1)) << np.uint64(q)
+        out[:, 1] |= ((z >> s) & np.uint64(1)) << np.uint64(q)
+    return out
+
+
+def test_packed_of_is_pack_rows():
+    rng = np.random.default_rng(800)
+    x, z = rng.integers(0, 1 << 20, 300), rng.integers(0, 1 << 20, 300)
+    assert np.array_equal(_packed_of(x, z, 20), packing.pack_rows(po.symp_of(x, z, 20)).reshape(300, 2))
+
+
+@pytest.mark.parametrize('which', ['three diagonals', 'density 0.3', 'duplicates, unsorted', 'coo with duplicates', 'csc', 'stored zeros'])
+def test_int64_csr_indices_equal_int32(monkeypatch, which):
+    n, inputs = _csr_inputs()
+    m = scipy.sparse.csr_matrix(inputs[which], dtype=np.complex128, copy=True)
+    m.sum_duplicates()
+    m.sort_indices()
+    if which == 'stored zeros':
+        assert np.count_nonzero(m.data == 0) > 100               # kept: a stored zero is an entry like any other
+    expect = po.decompose(m.toarray(), n)
+    for width in (np.int32, np.int64):
+        idx, ptr = m.indices.astype(width), m.indptr.astype(width)
+        for res in _in_both_forms(monkeypatch, n, lambda: kernels.pauli_decompose_csr(m.data, idx, ptr, n)):
+            rows, coeff, t = _terms_of(res)
+            assert np.array_equal(rows, _packed_of(expect[0], expect[1], n)), width
+            assert po.bits_equal(coeff, expect[2]), width
+
+
+def test_int64_csr_indices_with_a_basis(monkeypatch):
+    n = 7
+    rng = np.random.default_rng(410)
+    m = gaussian(rng, (1 << n, 1 << n))
+    m[rng.random(m.shape) >= 0.2] = 0
+    sp = scipy.sparse.csr_matrix(m)
+    bx, bz = rng.integers(0, 1 << n, 50).astype('<u8'), rng.integers(0, 1 << n, 50).astype('<u8')
+    full = po.coefficients_of_diagonals(po.diagonals(m, np.arange(1 << n)), np.arange(1 << n), n)
+    want = full[bx.astype(np.int64), bz.astype(np.int64)]
+    for width in (np.int32, np.int64):
+        idx, ptr = sp.indices.astype(width), sp.indptr.astype(width)
+        for c, _ in _in_both_forms(monkeypatch, n, lambda: kernels.pauli_decompose_csr(sp.data, idx, ptr, n, bx, bz)):
+            assert po.bits_equal(c, want), width
+
+
+@pytest.mark.parametrize('n, name', [(n, name) for n in sorted(fam.BLOCK_BASES) for name in fam.BLOCK_BASES[n]])
+def test_dense_input_with_block_bases(monkeypatch, n, name):
+    """The basis path of k_pd_gather_dense: blocks of 32 X-parts with bit 0 only, bit 31 only, all 32 bits, absent blocks, the last
+    block of the range (tests/test_csr_families.py proves the masks).  The matrix is full, so a diagonal gathered into the wrong rank
+    or from the wrong block brings other numbers."""
+    bx, bz, facts = fam.block_basis(n, name)
+    M = gaussian(np.random.default_rng(900 + n), (1 << n, 1 << n))
+    full = po.coefficients_of_diagonals(po.diagonals(M, np.arange(1 << n)), np.arange(1 << n), n)
+    want = full[bx.astype(np.int64), bz.astype(np.int64)]
+    assert want.shape == (facts['K'],) and np.all(want != 0)
+    for c, _ in _in_both_forms(monkeypatch, n, lambda: kernels.pauli_decompose_dense(M, n, bx, bz)):
+        assert po.bits_equal(c, want), 'dense input'
+    sp = scipy.sparse.csr_matrix(M)
+    for c, _ in _in_both_forms(monkeypatch, n, lambda: kernels.pauli_decompose_csr(sp.data, sp.indices, sp.indptr, n, bx, bz)):
+        assert po.bits_equal(c, want), 'CSR input'
+
+
+_N20 = {}
+
+
+def _n20():
+    """Two diagonals of 2^20 Gaussian entries on the X-parts of the large-n family, as CSR arrays, and the restatement's coefficients of
+    both diagonals (built once, shared, not written to)."""
+    if not _N20:
+        n, side = 20, 1 << 20
+        symp, _, facts = fam.large_n(n)
+        xs = np.array([x for x in facts['x_parts'] if x], dtype=np.int64)
+        assert len(xs) == 2 and xs[0] == 1 << 19 and xs[1] & 1 and xs[1] > xs[0]
+        diag = gaussian(np.random.default_rng(430), (2, side))
+        b = np.arange(side, dtype=np.int64)
+        sp = scipy.sparse.coo_matrix((diag.reshape(-1), (np.tile(b, 2), np.concatenate([b ^ xs[0], b ^ xs[1]]))), shape=(side, side)).tocsr()
+        sp.sort_indices()
+        _N20.update(n=n, xs=xs, sp=sp, coeff=po.coefficients_of_diagonals(diag, xs, n))
+    return _N20
+
+
+@pytest.mark.parametrize('width', [np.int32, np.int64])
+def test_n20_natural_two_pass(monkeypatch, width):
+    monkeypatch.delenv('SYMGPU_PAULI_TILE_BITS', raising=False)
+    g = _n20()
+    n, sp, xs, c = g['n'], g['sp'], g['xs'], g['coeff']
+    idx, ptr = sp.indices.astype(width), sp.indptr.astype(width)
+    res = kernels.pauli_decompose_csr(sp.data, idx, ptr, n)
+    assert res[2] == kernels.PAULI_TWO_PASS                           # 13 bits in contiguous tiles, 7 in one strided launch
+    rows, coeff, t = _terms_of(res)
+    keep = ~((c.real == 0) & (c.imag == 0))
+    j, z = np.nonzero(keep)
+    assert t == len(j) and t > 2 * (1 << n) - 16
+    assert np.array_equal(rows, _packed_of(xs[j], z, n))
+    assert po.bits_equal(coeff, c[keep])
+    # a basis of 50 picks: both diagonals and one X-part that the matrix does not have
+    rng = np.random.default_rng(431)
+    absent = 0x2A5B
+    bx = rng.choice(np.array([xs[0], xs[1], absent]), 50).astype('<u8')
+    bz = rng.integers(0, 1 << n, 50).astype('<u8')
+    assert {int(v) for v in bx} == {int(xs[0]), int(xs[1]), absent}
+    picked, form = kernels.pauli_decompose_csr(sp.data, idx, ptr, n, bx, bz)
+    want = np.where(bx == absent, 0, c[np.searchsorted(xs, np.minimum(bx.astype(np.int64), xs[1])), bz.astype(np.int64)])
+    assert form == kernels.PAULI_TWO_PASS and po.bits_equal(picked, want)
+
+
+def test_round_trip_at_19_qubits():
+    """P -> to_csr with int64 indices -> pauli_decompose_csr on those very arrays -> P's terms in (x, z) order, bit for bit (dyadic:
+    the 2^19 entries of a diagonal sum exactly)."""
+    n = 19
+    symp, c, facts = fam.large_n(n)
+    data, indices, indptr = kernels.to_csr(PauliwordOp(symp, c)._device(), n, index_dtype=np.int64)
+    assert indices.dtype == np.int64 and indptr.dtype == np.int64 and len(data) == facts['nnz']
+    rows, coeff, t = _terms_of(kernels.pauli_decompose_csr(data, indices, indptr, n))
+    x, z = po.xz_of(symp)
+    order = np.lexsort((z, x))
+    assert t == 6 and np.array_equal(rows, _packed_of(x[order], z[order], n))
+    assert np.array_equal(rows, packing.pack_rows(symp[order]).reshape(6, 2))
+    assert po.bits_equal(coeff, c[order])
+
+
+@pytest.mark.parametrize('width', [np.int32, np.int64])
+def test_empty_and_one_entry_csr(width):
+    n = 3
+    none = np.zeros(0, dtype=np.complex128)
+    idx, ptr = np.zeros(0, dtype=width), np.zeros((1 << n) + 1, dtype=width)
+    rows, coeff, t = _terms_of(kernels.pauli_decompose_csr(none, idx, ptr, n))
+    assert t == 0 and rows.shape[0] == 0 and coeff.shape == (0,)
+    bx, bz = np.array([0, 7, 3, 0], dtype='<u8'), np.array([1, 7, 0, 0], dtype='<u8')
+    picked, _ = kernels.pauli_decompose_csr(none, idx, ptr, n, bx, bz)
+    assert po.bits_equal(picked, np.zeros(4, dtype=np.complex128))
+    # one qubit, one stored entry: M = [[0, 2 - i], [0, 0]] = (1 - i/2) X + (1/2 + i) Y
+    M = np.array([[0, 2 - 1j], [0, 0]])
+    dev, t, form = kernels.pauli_decompose_csr(np.array([2 - 1j]), np.array([1], dtype=width), np.array([0, 1, 1], dtype=width), 1)
+    assert form == kernels.PAULI_ONE_PASS
+    expect = po.decompose(M, 1)
+    assert expect[0].tolist() == [1, 1] and expect[1].tolist() == [0, 1] and expect[2].tolist() == [1 - 0.5j, 0.5 + 1j]
+    assert_is_restatement(PauliwordOp._from_device(dev, 1, t), 1, expect)
