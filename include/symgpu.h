@@ -72,50 +72,105 @@ int symgpu_timer_stop(float *ms);
 #define SYMGPU_PROF_CLASSES 6
 int symgpu_prof_enable(int kernel_class, int on);
 int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
-/* statistics for tests: which = 0: number of row-hash collisions that forced the cleanup to reseed its hash and retry (the exactness
- * guard behind symplectic_cleanup, operators/utils.py:230-279; expected 0 outside the tests, which weaken the hash on purpose);
- * 1: rotations completed by the one-launch LDS-resident kernel; 2: calls of that kernel that reported a failed row verification or a
- * barrier time-out (the multi-launch path then recomputes); 3: device allocations that were not served from the allocator's arena;
- * 4-6: host nanoseconds spent by the one-launch rotation in preparation, in the launch call and waiting for the kernel's status word;
- * 7 / 8: payload bytes copied host -> device / device -> host by this library (operators, coefficients, index arrays, result matrices; not the
- * few-byte counts and flags a call reads back); 9 / 10: operator uploads / downloads (calls that moved a whole operator or its coefficients).
- * The drop-in classes keep their operands on the device between calls; the tests assert through 7-10 that a multi-step workflow
- * (symmer/projection/base.py:44-124, rotate -> project -> cleanup) moves its operator once in and once out.  11: device blocks whose
- * guard bytes were overwritten (tuning build, SYMGPU_ALLOC_CANARY); 12: the most threads seen using one device's context at once since
- * load, counted where a call uses the context's state, whichever lock it took (1 while the per-device lock holds); 13: calls that found
- * their device busy with another thread's call and waited; 14: uses of a device's context by a call that did not hold that context's
- * lock (0 while the lock is taken on the right device).  15: blocks (of up to 64 rows) panelled by the blocked GF(2) elimination since
- * load — the one-workgroup path for matrices of at most 64 rows and 64 words counts none; 16: of these, the blocks whose panel ran on the
- * full rows in LDS; 17: of these, the blocks whose panel ran on the two-word window (the rest took the four-word window, or held zero rows
- * only).  A reduction that is redone after an in-launch time-out counts both runs.  tests/test_gpu_gf2_structure.py asserts through
- * them which panel a matrix family took.  18 / 19: commutation calls (symgpu_commutes, symgpu_commutes_dev, symgpu_commutes_bits_dev and
- * what is built on them) served by the register-tile kernel / by the wide-row kernel; 20 / 21: launches of the Four-Russians commutation
- * kernel with one tile per workgroup / as stream-K (persistent workgroups over the (tile, step) space; a stream-K request with fewer tiles
- * than compute units counts as 20).  A call with no rows on either side counts nothing.  tests/test_gpu_commute_families.py asserts
- * through them which kernel a call took.  22 .. 26: runs of Clifford rotations (symgpu_rotate_clifford_chain_dev with at least one row and
- * one rotation, and the runs that symgpu_perform_rotations_dev hands to it) served by the register chain / the LDS-resident kernel / the
- * single-workgroup kernel / the two-launch form / the four-launch form; 27 / 28: segments (of up to 40 rotations) of the register chain whose
- * keys were sorted by the one-launch sort / by the multi-launch sort (a run that is redone after a time-out of the one-launch sort counts
- * both).  29 / 30 / 31: single rotations (symgpu_rotate_single_dev) completed by the hash join / by the Clifford fast path / by the general
- * path (stack + cleanup); 32: of 31, odd-k Clifford rotations whose duplicate check found two equal rows.  Rotations completed by the
- * one-launch kernel are counted by 1 alone.  tests/test_gpu_rotation_families.py asserts through 22-32 which form and stage ran.
- * 33 / 34 / 35: one-launch rotations LAUNCHED (completed or not) with each block's rows in LDS / in LDS and registers / left in memory;
- * tests/test_gpu_rotate_resident.py and the full-size tests assert through them which form a shape took.
- * 36 .. 47: the fused product + cleanup (symgpu_mul_cleanup*, and what is built on them), counted once per ATTEMPT of a call (a call
- * that reseeds the row hash or repeats with the full sort counts every attempt).  36: the packed pair keys were ordered by the complete
- * sort, no flag pass; 37 / 38: the flag pass was launched from the bucketed operand hash tables / behind the partial sort; 39: a flag pass
- * came back with its give-up word set; 40 / 41 / 42 / 43: of 39, the hash-table pass by reason (one each for every reason it reported): a
- * product bucket of more than 16,384 pairs / a saturated 4-bit counter / an overflowing list / an operand bucket of more than 255 terms;
- * 44: the sort was finished on the whole array after the flag pass (most keys flagged, a give-up, or SYMGPU_CLEANUP_SUSPECTS=2); 45: the
- * flagged keys were sorted alone; 46: the single terms were marked from one byte per pair; 47: the attempt was repeated with the full 64-bit
- * sort (a long run of equal key prefixes that holds different keys).  Calls on 64-bit keys with an index sort (plain cleanups,
- * SYMGPU_CLEANUP_UNPACKED=1, index fields over 32 bits) count none of 36 .. 46.  48 .. 52: calls of symgpu_mul_allpairs_dev (and of
- * symgpu_mul_allpairs) with at least one pair to form (counted before the path runs, whether or not it succeeds), by path: rows only / phase-byte row stream / wide coefficient kernel, then rows /
- * word-major coefficient kernel, then rows / the same beside the rows on a second stream.  tests/test_gpu_pair_flows.py and
- * tests/test_gpu_product_coeff_stage.py assert through them which flow and path a call took.  53 / 54: launches of the fill kernel of
- * symgpu_to_csr_fill (k_csr_fill) with its slots in LDS / in global scratch: one per call in LDS, one per chunk of workgroups whose slots
- * fit the scratch limit otherwise.  tests/test_gpu_csr_families.py asserts through them which form a shape took and in how many launches. */
+/* Statistics for tests: the counters of symgpu_debug_counter, each exactly once, as X(NAME, id, "what it counts").  The ids are part of
+ * the ABI and never change; the enum below, the library's array and symgpu_debug_counter_name are generated from this list.
+ * All counts are per process, since load. */
+#define SYMGPU_COUNTER_LIST(X) \
+    X(HASH_RESEEDS, 0, "number of row-hash collisions that forced the cleanup to reseed its hash and retry (the exactness guard behind " \
+      "symplectic_cleanup, operators/utils.py:230-279; expected 0 outside the tests, which weaken the hash on purpose)") \
+    X(RESIDENT_DONE, 1, "rotations completed by the one-launch LDS-resident kernel") \
+    X(RESIDENT_FAILED, 2, "calls of that kernel that reported a failed row verification or a barrier time-out (the multi-launch path then " \
+      "recomputes)") \
+    X(DEV_MALLOC_CALLS, 3, "device allocations that were not served from the allocator's arena") \
+    X(RESIDENT_NS_PREPARE, 4, "host nanoseconds spent by the one-launch rotation in preparation") \
+    X(RESIDENT_NS_LAUNCH, 5, "host nanoseconds spent by the one-launch rotation in the launch call") \
+    X(RESIDENT_NS_WAIT, 6, "host nanoseconds spent by the one-launch rotation waiting for the kernel's status word") \
+    /* The drop-in classes keep their operands on the device between calls; the tests assert through 7-10 that a multi-step workflow
+     * (symmer/projection/base.py:44-124, rotate -> project -> cleanup) moves its operator once in and once out. */ \
+    X(H2D_BYTES, 7, "payload bytes copied host -> device by this library (operators, coefficients, index arrays, result matrices; not the " \
+      "few-byte counts and flags a call reads back)") \
+    X(D2H_BYTES, 8, "payload bytes copied device -> host by this library (as 7)") \
+    X(OP_UPLOADS, 9, "operator uploads (calls that moved a whole operator or its coefficients)") \
+    X(OP_DOWNLOADS, 10, "operator downloads (calls that moved a whole operator or its coefficients)") \
+    X(CANARY_HITS, 11, "device blocks whose guard bytes were overwritten (tuning build, SYMGPU_ALLOC_CANARY)") \
+    X(CTX_MAX_THREADS, 12, "the most threads seen using one device's context at once since load, counted where a call uses the context's " \
+      "state, whichever lock it took (1 while the per-device lock holds)") \
+    X(CTX_WAITS, 13, "calls that found their device busy with another thread's call and waited") \
+    X(CTX_UNLOCKED_USES, 14, "uses of a device's context by a call that did not hold that context's lock (0 while the lock is taken on the " \
+      "right device)") \
+    /* 15-17: a reduction that is redone after an in-launch time-out counts both runs.  tests/test_gpu_gf2_structure.py asserts through
+     * them which panel a matrix family took. */ \
+    X(GF2_BLOCKS_PANELLED, 15, "blocks (of up to 64 rows) panelled by the blocked GF(2) elimination since load - the one-workgroup path for " \
+      "matrices of at most 64 rows and 64 words counts none") \
+    X(GF2_PANEL_FULL_ROWS, 16, "of 15, the blocks whose panel ran on the full rows in LDS") \
+    X(GF2_PANEL_WINDOW, 17, "of 15, the blocks whose panel ran on the two-word window (the rest took the four-word window, or held zero " \
+      "rows only)") \
+    /* 18-21: a call with no rows on either side counts nothing.  tests/test_gpu_commute_families.py asserts through them which kernel a
+     * call took. */ \
+    X(COMMUTE_REGISTER_TILE, 18, "commutation calls (symgpu_commutes, symgpu_commutes_dev, symgpu_commutes_bits_dev and what is built on " \
+      "them) served by the register-tile kernel") \
+    X(COMMUTE_WIDE_ROWS, 19, "commutation calls served by the wide-row kernel") \
+    X(COMMUTE_M4R_TILE, 20, "launches of the Four-Russians commutation kernel with one tile per workgroup (a stream-K request with fewer " \
+      "tiles than compute units counts here)") \
+    X(COMMUTE_M4R_STREAMK, 21, "launches of the Four-Russians commutation kernel as stream-K (persistent workgroups over the (tile, step) " \
+      "space)") \
+    /* 22-32: tests/test_gpu_rotation_families.py asserts through them which form and stage ran.  Rotations completed by the one-launch
+     * kernel are counted by 1 alone. */ \
+    X(CHAIN_REGISTERS, 22, "runs of Clifford rotations (symgpu_rotate_clifford_chain_dev with at least one row and one rotation, and the " \
+      "runs that symgpu_perform_rotations_dev hands to it) served by the register chain") \
+    X(CHAIN_LDS, 23, "runs of Clifford rotations served by the LDS-resident kernel") \
+    X(CHAIN_SINGLE_WORKGROUP, 24, "runs of Clifford rotations served by the single-workgroup kernel") \
+    X(CHAIN_TWO_LAUNCHES, 25, "runs of Clifford rotations served by the two-launch form") \
+    X(CHAIN_FOUR_LAUNCHES, 26, "runs of Clifford rotations served by the four-launch form") \
+    X(CHAIN_SORT_ONE_LAUNCH, 27, "segments (of up to 40 rotations) of the register chain whose keys were sorted by the one-launch sort (a " \
+      "run that is redone after a time-out of the one-launch sort counts 27 and 28)") \
+    X(CHAIN_SORT_LAUNCHES, 28, "segments (of up to 40 rotations) of the register chain whose keys were sorted by the multi-launch sort") \
+    X(ROTATE_HASH_JOIN, 29, "single rotations (symgpu_rotate_single_dev) completed by the hash join") \
+    X(ROTATE_CLIFFORD_FAST, 30, "single rotations completed by the Clifford fast path") \
+    X(ROTATE_GENERAL, 31, "single rotations completed by the general path (stack + cleanup)") \
+    X(ROTATE_GENERAL_BY_DUP_CHECK, 32, "of 31, odd-k Clifford rotations whose duplicate check found two equal rows") \
+    /* 33-35: tests/test_gpu_rotate_resident.py and the full-size tests assert through them which form a shape took. */ \
+    X(RESIDENT_LDS, 33, "one-launch rotations LAUNCHED (completed or not) with each block's rows in LDS") \
+    X(RESIDENT_REGISTERS, 34, "one-launch rotations LAUNCHED (completed or not) with each block's rows in LDS and registers") \
+    X(RESIDENT_ROWS_IN_MEMORY, 35, "one-launch rotations LAUNCHED (completed or not) with each block's rows left in memory") \
+    /* 36-47: the fused product + cleanup (symgpu_mul_cleanup*, and what is built on them), counted once per ATTEMPT of a call (a call
+     * that reseeds the row hash or repeats with the full sort counts every attempt).  Calls on 64-bit keys with an index sort (plain
+     * cleanups, SYMGPU_CLEANUP_UNPACKED=1, index fields over 32 bits) count none of 36-46.  tests/test_gpu_pair_flows.py and
+     * tests/test_gpu_product_coeff_stage.py assert through 36-52 which flow and path a call took. */ \
+    X(FLOW_COMPLETE_SORT, 36, "the packed pair keys were ordered by the complete sort, no flag pass") \
+    X(FLOW_FLAGS_HASH_TABLES, 37, "the flag pass was launched from the bucketed operand hash tables") \
+    X(FLOW_FLAGS_PARTIAL_SORT, 38, "the flag pass was launched behind the partial sort") \
+    X(FLOW_FLAGS_GAVE_UP, 39, "a flag pass came back with its give-up word set") \
+    X(GIVEUP_PRODUCT_BUCKET, 40, "of 39, the hash-table pass by reason (one each for every reason it reported): a product bucket of more " \
+      "than 16,384 pairs") \
+    X(GIVEUP_COUNTER_SATURATED, 41, "of 39, the hash-table pass by reason: a saturated 4-bit counter") \
+    X(GIVEUP_LIST_OVERFLOW, 42, "of 39, the hash-table pass by reason: an overflowing list") \
+    X(GIVEUP_OPERAND_BUCKET, 43, "of 39, the hash-table pass by reason: an operand bucket of more than 255 terms") \
+    X(FLOW_SORTED_WHOLE, 44, "the sort was finished on the whole array after the flag pass (most keys flagged, a give-up, or " \
+      "SYMGPU_CLEANUP_SUSPECTS=2)") \
+    X(FLOW_SORTED_FLAGGED, 45, "the flagged keys were sorted alone") \
+    X(FLOW_MARKED_FROM_BYTES, 46, "the single terms were marked from one byte per pair") \
+    X(FLOW_FULL_SORT_REPEAT, 47, "the attempt was repeated with the full 64-bit sort (a long run of equal key prefixes that holds " \
+      "different keys)") \
+    /* 48-52: calls of symgpu_mul_allpairs_dev (and of symgpu_mul_allpairs) with at least one pair to form (counted before the path runs,
+     * whether or not it succeeds), by path. */ \
+    X(PRODUCT_ROWS_ONLY, 48, "all-pairs products by path: rows only") \
+    X(PRODUCT_PHASE_STREAM, 49, "all-pairs products by path: phase-byte row stream") \
+    X(PRODUCT_WIDE_COEFF_THEN_ROWS, 50, "all-pairs products by path: wide coefficient kernel, then rows") \
+    X(PRODUCT_WORD_MAJOR_THEN_ROWS, 51, "all-pairs products by path: word-major coefficient kernel, then rows") \
+    X(PRODUCT_WORD_MAJOR_BESIDE_ROWS, 52, "all-pairs products by path: the same beside the rows on a second stream") \
+    /* 53 / 54: one per call in LDS, one per chunk of workgroups whose slots fit the scratch limit otherwise.
+     * tests/test_gpu_csr_families.py asserts through them which form a shape took and in how many launches. */ \
+    X(CSR_FILL_LDS, 53, "launches of the fill kernel of symgpu_to_csr_fill (k_csr_fill) with its slots in LDS") \
+    X(CSR_FILL_SCRATCH, 54, "launches of the fill kernel of symgpu_to_csr_fill (k_csr_fill) with its slots in global scratch")
+#define SYMGPU_COUNTER_ENUM_ENTRY(name, id, text) SYMGPU_CTR_##name = id,
+typedef enum symgpu_counter { SYMGPU_COUNTER_LIST(SYMGPU_COUNTER_ENUM_ENTRY) SYMGPU_CTR_COUNT = 55 } symgpu_counter;
+#undef SYMGPU_COUNTER_ENUM_ENTRY
+/* *value = the counter `which` (an id of the list above; SYMGPU_E_INVALID outside it).  Needs no device and no context. */
 int symgpu_debug_counter(int which, int64_t *value);
+/* The name of counter `which` as spelled in the list ("HASH_RESEEDS", ...), NULL outside 0 .. 54: a binder builds its name -> id map from
+ * it instead of copying numbers.  Needs no device and no context. */
+const char *symgpu_debug_counter_name(int which);
 /* The radix sort and the two scans that everything else stands on, run directly on device buffers of the caller's (symgpu_dev_alloc /
  * symgpu_dev_upload), for tests/test_gpu_sort.py.  All three return after a stream synchronisation.
  *  debug_sort       sorts keys[0..n) (and vals[0..n) with them, if not NULL) in place by key bits [begin_bit, end_bit) (a multiple of 8

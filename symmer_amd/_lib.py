@@ -44,6 +44,7 @@ SIGNATURES = {
     'symgpu_prof_enable': [c_int, c_int],
     'symgpu_prof_read': [c_int, P, P],
     'symgpu_debug_counter': [c_int, P],
+    'symgpu_debug_counter_name': [c_int],           # returns const char *
     'symgpu_debug_sort': [P, P, c_i64, c_int, c_int, c_int, c_int, P],
     'symgpu_debug_scan': [P, P, c_i64, P],
     'symgpu_debug_popc_scan': [P, c_i64, c_i64, P, P],
@@ -145,8 +146,24 @@ def load():
         fn.restype = c_int
     lib.symgpu_last_error.restype = ctypes.c_char_p
     lib.symgpu_last_error.argtypes = []
+    lib.symgpu_debug_counter_name.restype = ctypes.c_char_p
     _lib = lib
     return lib
+
+
+_counter_ids = None
+
+
+def counter_ids():
+    """{name: id} of the library's debug counters (SYMGPU_COUNTER_LIST of include/symgpu.h), read from the library itself; no GPU call."""
+    global _counter_ids
+    if _counter_ids is None:
+        name_of, ids, which = load().symgpu_debug_counter_name, {}, 0
+        while name_of(which) is not None:
+            ids[name_of(which).decode('ascii')] = which
+            which += 1
+        _counter_ids = ids
+    return _counter_ids
 
 
 def last_error():

@@ -66,7 +66,7 @@ static void *arena_carve(DevAlloc &A, size_t c, int *chunk) {
         }
         if (pass == 1) break;
         void *base = nullptr;
-        bump_counter(3);
+        bump_counter(SYMGPU_CTR_DEV_MALLOC_CALLS);
         if (hipMalloc(&base, ARENA_CHUNK) != hipSuccess) { (void)hipGetLastError(); A.arena_on = false; return nullptr; }
         A.chunks.push_back(Chunk{static_cast<char *>(base), ARENA_CHUNK, 0, 0});
     }
@@ -88,7 +88,7 @@ static void canary_check(void *p, size_t bytes) {
     for (size_t k = 0; k < CANARY; ++k)
         if (h[k] != 0xA5) {
             fprintf(stderr, "symgpu CANARY: block of %zu bytes overwritten at +%zu behind its end (value 0x%02x)\n", bytes, k, h[k]);
-            bump_counter(11);
+            bump_counter(SYMGPU_CTR_CANARY_HITS);
             return;
         }
 }
@@ -143,7 +143,7 @@ int dev_alloc(size_t bytes, void **ptr) {
         }
     }
     std::lock_guard<std::mutex> lk(g_alloc_mu);
-    bump_counter(3);
+    bump_counter(SYMGPU_CTR_DEV_MALLOC_CALLS);
     record_live(*ptr, LiveBlock{c, -1, dev, req});
     return SYMGPU_OK;
 }

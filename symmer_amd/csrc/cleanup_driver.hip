@@ -158,9 +158,9 @@ static int cleanup_run(const CleanupRequest &rq, symgpu_op_t *out) {
             radix_sort_coop_note(hback[3], &timed_out);
             if (timed_out) continue;
         }
-        if (hback[2]) { bump_counter(47); r.pl = plan_cleanup(rq, r.sw, true); continue; }   // a long mixed prefix run: redo with a full 64-bit sort over all pairs, same seed
+        if (hback[2]) { bump_counter(SYMGPU_CTR_FLOW_FULL_SORT_REPEAT); r.pl = plan_cleanup(rq, r.sw, true); continue; }   // a long mixed prefix run: redo with a full 64-bit sort over all pairs, same seed
         ok = (hback[1] == 0);
-        if (!ok) { ++r.seed; g_hash_reseeds.fetch_add(1, std::memory_order_relaxed); }   // genuine 64-bit hash collision: reseed and retry
+        if (!ok) { ++r.seed; bump_counter(SYMGPU_CTR_HASH_RESEEDS); }   // genuine 64-bit hash collision: reseed and retry
     }
     if (!ok) { set_error("cleanup: 64-bit row-hash collision survived 4 reseeds"); return SYMGPU_E_COLLISION; }
     const PairOperands &p = rq.p;

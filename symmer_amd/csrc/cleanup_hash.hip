@@ -13,7 +13,6 @@ static u64 host_splitmix64(u64 &s) {
     return z ^ (z >> 31);
 }
 
-std::atomic<i64> g_hash_reseeds{0};   // statistics (symgpu_debug_counter 0)
 // k_hash_rows_long: columns of M^(2^j), M = the xorshift step of the per-lane Horner scheme (a linear map on GF(2)^64), j < 32
 static u64 host_xorshift_step(u64 h) { h ^= h << 13; h ^= h >> 7; h ^= h << 17; return h; }
 static int ensure_xs_pow() {

@@ -544,7 +544,7 @@ static int mark_singles_packed(CleanupRun &r) {
     const double *fl_i = r.cfloor.as<double>(), *fl_o = two_ops ? r.cfloor.as<double>() + 1 : r.cfloor.as<double>();
     if (r.sw.nofloor) fl_i = fl_o = nullptr;     // tests: every coefficient looked at
     if (pl.key_bytes) {
-        bump_counter(46);                                  // symgpu_debug_counter 46: the single terms marked from bytes
+        bump_counter(SYMGPU_CTR_FLOW_MARKED_FROM_BYTES);   // the single terms marked from bytes
         const i64 n_groups = (Tk + 63) / 64 * 4;           // whole 64-bit words of the bitmaps
         hipLaunchKernelGGL(k_mark_bytes, dim3((unsigned)grid_for(n_groups, 256, 1 << 16)), dim3(256), 0, st, r.keys.as<u32x4>(), Tk, n_groups, Ni, ci, co,
                            pl.squared ? 1 : 0, r.rq.thr, r.rq.use_thr, r.markbits.as<unsigned short>(), r.e_lo.as<unsigned short>(), r.e_hi.as<unsigned short>(), fl_i, fl_o);
@@ -616,7 +616,7 @@ static int order_flagged(CleanupRun &r) {
     bool direct = false;
     SG_TRY(pair_dups_dev(r.hI.as<u64>(), p.Ni, r.hO_p, p.No, pl.squared, Tk, susbits.as<u64>(), sustotal + 1, &direct));
     u64 *part = r.keys.as<u64>(), *spare = r.keys2.as<u64>();
-    bump_counter(direct ? 37 : 38);                        // which flag pass this attempt launches: symgpu_debug_counter 37 / 38
+    bump_counter(direct ? SYMGPU_CTR_FLOW_FLAGS_HASH_TABLES : SYMGPU_CTR_FLOW_FLAGS_PARTIAL_SORT);   // which flag pass this attempt launches
     if (!direct) {
         if (pl.key_bytes) SG_TRY(pair_keys(r, false));     // (the flag pass was refused: keys after all)
         SortResult res;
@@ -647,11 +647,11 @@ static int order_flagged(CleanupRun &r) {
     }
     const u32 h_sus = h_sus2[0];
     if (h_sus2[1]) {                                       // the flag pass gave up; the hash-table pass says why (the bits of k_pd_bucket / k_pair_dups)
-        bump_counter(39);
-        for (int b = 0; direct && b < 4; ++b) if ((h_sus2[1] >> b) & 1u) bump_counter(40 + b);
+        bump_counter(SYMGPU_CTR_FLOW_FLAGS_GAVE_UP);
+        for (u32 bit : PD_GIVEUP_BITS) if (direct && (h_sus2[1] & bit)) bump_counter(counter_of_giveup(bit));
     }
     if ((i64)h_sus * 16 > Tk || r.sw.suspects == 2 || h_sus2[1]) {
-        bump_counter(44);                                  // symgpu_debug_counter 44: the sort finished on the whole array
+        bump_counter(SYMGPU_CTR_FLOW_SORTED_WHOLE);        // the sort finished on the whole array
         // repeated rows all over: the last pass on the whole array after all (LSD: the order so far is its first passes; the
         // direct flag pass left the keys in index order: all passes)
         if (pl.key_bytes && direct) SG_TRY(pair_keys(r, false));   // (only bytes so far: the keys after all)
@@ -660,7 +660,7 @@ static int order_flagged(CleanupRun &r) {
         a.ks = res.keys;
         return SYMGPU_OK;
     }
-    bump_counter(45);                                      // symgpu_debug_counter 45: the flagged keys sorted alone (none flagged: nothing to sort)
+    bump_counter(SYMGPU_CTR_FLOW_SORTED_FLAGGED);          // the flagged keys sorted alone (none flagged: nothing to sort)
     a.sus_active = true;
     a.Tsort = h_sus;
     a.ks = part;
@@ -684,7 +684,7 @@ int cleanup_order(CleanupRun &r) {
     if (pl.sus_try) return order_flagged(r);
     // (plain cleanups of up to 1.3e5 rows: the index sort in ONE launch — its three passes were nine launches, launch bound;
     // small products — up to 2e5 keys, no first-pass histograms at hand —: the sort in ONE launch; its passes were three launches each)
-    if (pl.packed) bump_counter(36);                       // symgpu_debug_counter 36: the complete sort of the packed keys, no flag pass
+    if (pl.packed) bump_counter(SYMGPU_CTR_FLOW_COMPLETE_SORT);   // the complete sort of the packed keys, no flag pass
     SortResult res;
     SG_TRY(radix_sort({r.keys.as<u64>(), r.keys2.as<u64>(), pl.packed ? nullptr : r.idx.as<u32>(), pl.packed ? nullptr : r.idx2.as<u32>(), Tk, 64 - pl.nbits, 64,
                        a.first_hist, SortForm::OneLaunchWherePays}, &res));

@@ -61,7 +61,7 @@ struct EmitProbe { const void *key = nullptr; int phase = 0, choice = 0; u64 sta
 // leaves the lock and its counter where they are.
 struct ContextLock {
     std::recursive_mutex mu;
-    std::atomic<int> inside{0};           // threads whose open calls use this context right now (symgpu_debug_counter 12, context.hip ctx())
+    std::atomic<int> inside{0};           // threads whose open calls use this context right now (SYMGPU_CTR_CTX_MAX_THREADS, context.hip ctx())
     ContextLock() {}
     ContextLock(const ContextLock &) {}
     ContextLock &operator=(const ContextLock &) { return *this; }
@@ -138,34 +138,10 @@ void forget_bound_device();                // after a library (RCCL) may have ch
         if (!(_done.fetch_or(_bit) & _bit) && (expr)) _ok.fetch_or(_bit);                             \
         return (_ok.load() & _bit) != 0;                                                              \
     }())
-extern std::atomic<i64> g_counters[55];    // debug counters (symgpu_debug_counter): [1] one-launch rotations, [2] their failures, [3] hipMalloc calls of dev_alloc,
-                                           // [7] / [8] payload bytes host -> device / device -> host, [9] / [10] operator uploads / downloads (calls),
-                                           // [11] canary hits, [12] most threads seen using one context at once, [13] calls that waited for a busy context,
-                                           // [14] uses of a context by a call that did not hold its lock, [15] blocks panelled by the blocked GF(2)
-                                           // elimination, [16] / [17] of these: on the full rows in LDS / on the two-word window (gf2.hip),
-                                           // [18] / [19] commutation calls served by the register-tile / the wide-row kernel, [20] / [21] Four-Russians
-                                           // commutation launches with one tile per workgroup / stream-K (commute_driver.hip, one place each),
-                                           // [22] .. [26] runs of Clifford rotations served by the register chain / the LDS-resident kernel / the
-                                           // single-workgroup kernel / the two-launch / the four-launch form (rotate_driver.hip run_chain, nowhere
-                                           // else), [27] / [28] segments of the register chain whose keys went to the one-launch / the multi-launch
-                                           // sort (rotate_chain.hip), [29] / [30] / [31] single rotations completed by the hash join / the Clifford
-                                           // fast path / the general path, [32] of [31]: sent there by the duplicate check (symgpu_rotate_single_dev),
-                                           // [33] / [34] / [35] one-launch rotations launched with the rows in LDS / in LDS and registers / left in
-                                           // memory (rotate_resident_kernel.hip launch_resident, nowhere else),
-                                           // [36] .. [47] product + cleanup, per attempt of cleanup_run (cleanup_keys.hip, one place each; [47]:
-                                           // cleanup_driver.hip): [36] packed keys ordered by the complete sort (no flag pass), [37] / [38] the flag
-                                           // pass launched from the operand hash tables / behind the partial sort, [39] a flag pass came back with
-                                           // giveup != 0, [40] .. [43] of these, the hash-table pass by reason: product bucket over 16,384 pairs /
-                                           // counter saturated / list overflow / operand bucket over 255, [44] the sort finished on the whole array
-                                           // after the flag pass, [45] the flagged keys sorted alone, [46] single terms marked from bytes,
-                                           // [47] the attempt repeated with the full 64-bit sort,
-                                           // [48] .. [52] calls of symgpu_mul_allpairs_dev by ProductPath: rows only / phase stream / wide coefficients /
-                                           // word-major, then rows / word-major beside rows (product_driver.hip, at the switch),
-                                           // [53] / [54] launches of k_csr_fill with its slots in LDS / in global scratch (sparse_matrix.hip
-                                           // csr_fill_launch, nowhere else)
-inline void bump_counter(int which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
-inline void count_h2d(size_t bytes) { bump_counter(7, (i64)bytes); }
-inline void count_d2h(size_t bytes) { bump_counter(8, (i64)bytes); }
+extern std::atomic<i64> g_counters[SYMGPU_CTR_COUNT];   // debug counters (symgpu_debug_counter): one per entry of SYMGPU_COUNTER_LIST (symgpu.h)
+inline void bump_counter(symgpu_counter which, i64 by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
+inline void count_h2d(size_t bytes) { bump_counter(SYMGPU_CTR_H2D_BYTES, (i64)bytes); }
+inline void count_d2h(size_t bytes) { bump_counter(SYMGPU_CTR_D2H_BYTES, (i64)bytes); }
 int require_ctx();
 // A call that is handed operator handles runs on THEIR device for its duration (and refuses handles of different devices), else on the
 // thread's current device; once that device is settled the scope holds its context's lock until it ends, and the thread's own selection
@@ -331,7 +307,6 @@ int wide_mul_coeff_dev(const u64 *inner, const double *ci, i64 Ni, const u64 *ou
                        int inner_is_left, double *out_coeff, const PairKeyArgs *keys);
 
 // cleanup_hash.hip, cleanup_driver.hip
-extern std::atomic<i64> g_hash_reseeds;                         // row-hash collisions that forced a reseed (never seen outside the tests)
 int ensure_hash_tables(u64 seed);
 int hash_rows(const u64 *rows, i64 T, int W, u64 *out1);       // h1 of every row (current tables)
 u64 host_row_hash(const u64 *row, int W);                       // the same hash on the host
@@ -349,6 +324,14 @@ int cleanup_pairs(const PairOperands &p, double thr, int use_thr, symgpu_op_t *o
 
 // pair_dups.hip — the pairs of a product whose 64-bit key another pair shares, found without sorting the keys
 bool pair_dups_fits(i64 Ni, i64 No, bool squared, i64 Tk, int *B_out, int *sb_out = nullptr);      // host-side: would pair_dups_dev take this product?
+// why the pass gave up: the bits k_pd_bucket / k_pair_dups raise in *giveup, and the counter of each (order_flagged, cleanup_keys.hip)
+constexpr u32 PD_GIVEUP_PRODUCT_BUCKET = 1u, PD_GIVEUP_COUNTER_SATURATED = 2u, PD_GIVEUP_LIST_OVERFLOW = 4u, PD_GIVEUP_OPERAND_BUCKET = 8u;
+constexpr u32 PD_GIVEUP_BITS[4] = {PD_GIVEUP_PRODUCT_BUCKET, PD_GIVEUP_COUNTER_SATURATED, PD_GIVEUP_LIST_OVERFLOW, PD_GIVEUP_OPERAND_BUCKET};
+constexpr symgpu_counter counter_of_giveup(u32 bit) { return (symgpu_counter)(SYMGPU_CTR_GIVEUP_PRODUCT_BUCKET + __builtin_ctz(bit)); }
+static_assert(counter_of_giveup(PD_GIVEUP_PRODUCT_BUCKET) == SYMGPU_CTR_GIVEUP_PRODUCT_BUCKET &&
+              counter_of_giveup(PD_GIVEUP_COUNTER_SATURATED) == SYMGPU_CTR_GIVEUP_COUNTER_SATURATED &&
+              counter_of_giveup(PD_GIVEUP_LIST_OVERFLOW) == SYMGPU_CTR_GIVEUP_LIST_OVERFLOW &&
+              counter_of_giveup(PD_GIVEUP_OPERAND_BUCKET) == SYMGPU_CTR_GIVEUP_OPERAND_BUCKET, "the give-up bits and their counters are in one order");
 int pair_dups_dev(const u64 *hI, i64 Ni, const u64 *hO, i64 No, bool squared, i64 Tk, u64 *flags, u32 *giveup, bool *applies);
 
 // gf2.hip

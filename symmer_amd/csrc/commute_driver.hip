@@ -103,9 +103,9 @@ static CommutePlan plan_commutes(i64 N, i64 M, int Wq, bool same_operand, bool w
 }
 
 // ---- stages: A: N rows, B: M rows, row-major packed device pointers; exactly one of out / out_bits is non-null ---------------------
-// which kernel served the call: symgpu_debug_counter 18 (register tile) / 19 (wide rows) / 20, 21 (Four Russians, by launch)
+// which kernel served the call is counted here: register tile, wide rows, Four Russians (by launch)
 static int run_register_tile(const CommutePlan &pl, const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits) {
-    bump_counter(18);
+    bump_counter(SYMGPU_CTR_COMMUTE_REGISTER_TILE);
     const int W = 2 * Wq;
     Scratch at, bt;
     SG_TRY(at.alloc((size_t)pl.Npad * W * sizeof(u64)));
@@ -118,13 +118,13 @@ static int run_register_tile(const CommutePlan &pl, const u64 *A, i64 N, const u
 }
 
 static int run_wide_rows(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits) {
-    bump_counter(19);
+    bump_counter(SYMGPU_CTR_COMMUTE_WIDE_ROWS);
     return wide_commutes_dev(A, N, B, M, Wq, out, out_bits);
 }
 
 static int run_four_russians(const CommutePlan &pl, const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner) {
-    if (pl.stream) bump_counter(21);
-    else bump_counter(20);
+    if (pl.stream) bump_counter(SYMGPU_CTR_COMMUTE_M4R_STREAMK);
+    else bump_counter(SYMGPU_CTR_COMMUTE_M4R_TILE);
     Scratch bt_scratch, bits;
     const u64 *bt = nullptr;
     SG_TRY(m4r_bit_major(pl, B, M, 2 * Wq, b_owner, bt_scratch, &bt));

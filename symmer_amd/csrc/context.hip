@@ -28,11 +28,19 @@ static Context g_ctxs[SYMGPU_MAX_DEVICES];
 static int g_default_dev = -1;                    // the first device initialised in this process
 static thread_local int t_cur_dev = -1;           // this thread's selection (-1: the default)
 static thread_local int t_bound_dev = -1;         // the device hipSetDevice was last called with on this thread
-std::atomic<i64> g_counters[55] = {};   // symgpu_debug_counter 1..54 (0 is g_hash_reseeds, cleanup_hash.hip)
+std::atomic<i64> g_counters[SYMGPU_CTR_COUNT] = {};
+// the list holds every id 0 .. SYMGPU_CTR_COUNT - 1 once: all in range, as many as the array has slots, and no two alike (the `case` labels
+// of symgpu_debug_counter_name)
+#define SG_COUNTER_IN_RANGE(name, id, text) static_assert(id >= 0 && id < SYMGPU_CTR_COUNT, "SYMGPU_COUNTER_LIST: id of " #name " out of range");
+#define SG_COUNTER_ONE(name, id, text) +1
+SYMGPU_COUNTER_LIST(SG_COUNTER_IN_RANGE)
+static_assert(0 SYMGPU_COUNTER_LIST(SG_COUNTER_ONE) == SYMGPU_CTR_COUNT, "SYMGPU_COUNTER_LIST: an id is missing");
+#undef SG_COUNTER_ONE
+#undef SG_COUNTER_IN_RANGE
 int cur_index() { return t_cur_dev >= 0 ? t_cur_dev : (g_default_dev >= 0 ? g_default_dev : 0); }
 // Use of a context inside a call, recorded where the state is used (ctx()), whatever lock the call's DeviceScope took: a thread that
-// uses a context whose lock it does not hold is counted (symgpu_debug_counter 14), and so are the threads that use one context at the
-// same time (the most of them: counter 12).  Calls that take no lock on purpose (symgpu_comm_*, init, shutdown) open no scope and are
+// uses a context whose lock it does not hold is counted (SYMGPU_CTR_CTX_UNLOCKED_USES), and so are the threads that use one context at the
+// same time (the most of them: SYMGPU_CTR_CTX_MAX_THREADS).  Calls that take no lock on purpose (symgpu_comm_*, init, shutdown) open no scope and are
 // not looked at.
 static thread_local int t_scopes = 0;                            // DeviceScopes open on this thread
 static thread_local int t_held[SYMGPU_MAX_DEVICES] = {};         // this thread's holds on each context's lock
@@ -76,10 +84,10 @@ void forget_bound_device() { t_bound_dev = -1; }
 
 static void note_use(int d) {
     t_using |= 1u << d;
-    if (t_held[d] == 0) bump_counter(14);                       // the call uses a context whose lock it does not hold
+    if (t_held[d] == 0) bump_counter(SYMGPU_CTR_CTX_UNLOCKED_USES);   // the call uses a context whose lock it does not hold
     const i64 users = g_ctxs[d].lock.inside.fetch_add(1) + 1;
-    i64 most = g_counters[12].load(std::memory_order_relaxed);
-    while (users > most && !g_counters[12].compare_exchange_weak(most, users, std::memory_order_relaxed)) {}
+    i64 most = g_counters[SYMGPU_CTR_CTX_MAX_THREADS].load(std::memory_order_relaxed);
+    while (users > most && !g_counters[SYMGPU_CTR_CTX_MAX_THREADS].compare_exchange_weak(most, users, std::memory_order_relaxed)) {}
 }
 
 int DeviceScope::enter(const symgpu_op_s *a, const symgpu_op_s *b, const symgpu_op_s *c) {
@@ -98,7 +106,7 @@ int DeviceScope::enter(const symgpu_op_s *a, const symgpu_op_s *b, const symgpu_
     const int d = cur_index();                        // the device the call runs on: the handles', else the thread's selection
     Context &cx = g_ctxs[d];
     if (!cx.lock.mu.try_lock()) {
-        bump_counter(13);                             // another thread's call is running on this device: wait for it to end
+        bump_counter(SYMGPU_CTR_CTX_WAITS);           // another thread's call is running on this device: wait for it to end
         cx.lock.mu.lock();
     }
     held = d;
@@ -378,9 +386,18 @@ int symgpu_prof_enable(int kernel_class, int on) {
 }
 
 int symgpu_debug_counter(int which, int64_t *value) {
-    SG_REQUIRE(value && which >= 0 && which <= 54, "debug_counter: 0 = row-hash reseeds, 1 = rotations done by the one-launch kernel, 2 = its failures (verification / time-out), 3 = device allocations that went to hipMalloc, 4-6 = host nanoseconds of the one-launch rotation (preparation, launch call, wait), 7 / 8 = payload bytes host -> device / device -> host, 9 / 10 = operator uploads / downloads, 11 = canary hits (tuning build), 12 = most threads seen using one device's context at once (1: the calls were serialised), 13 = calls that waited for another thread's call on their device, 14 = uses of a context by a call that did not hold its lock, 15 = blocks panelled by the blocked GF(2) elimination, 16 / 17 = of these, on the full rows in LDS / on the two-word window, 18 / 19 = commutation calls served by the register-tile / the wide-row kernel, 20 / 21 = Four-Russians commutation launches with one tile per workgroup / stream-K, 22-26 = runs of Clifford rotations by form (registers, LDS, single workgroup, two launches, four launches), 27 / 28 = register-chain segments sorted in one launch / by the multi-launch sort, 29-31 = single rotations completed by the hash join / the Clifford fast path / the general path, 32 = of 31, sent there by the duplicate check, 33-35 = one-launch rotations launched by form (rows in LDS, in LDS and registers, left in memory), 36-47 = product + cleanup, per attempt: 36 = packed keys ordered by the complete sort, 37 / 38 = flag pass from the operand hash tables / behind the partial sort, 39 = a flag pass gave up, 40-43 = the hash-table pass gave up because of a product bucket over 16,384 pairs / a saturated counter / a list overflow / an operand bucket over 255, 44 = the sort finished on the whole array after the flag pass, 45 = the flagged keys sorted alone, 46 = single terms marked from bytes, 47 = the attempt repeated with the full 64-bit sort, 48-52 = all-pairs products by path (rows only, phase stream, wide coefficients, word-major then rows, word-major beside rows), 53 / 54 = launches of the to_sparse_matrix fill (k_csr_fill) with its slots in LDS / in global scratch");
-    *value = (which == 0 ? g_hash_reseeds : g_counters[which]).load(std::memory_order_relaxed);
+    SG_REQUIRE(value && which >= 0 && which < SYMGPU_CTR_COUNT, "debug_counter: which is an id of SYMGPU_COUNTER_LIST (include/symgpu.h; symgpu_debug_counter_name spells them)");
+    *value = g_counters[which].load(std::memory_order_relaxed);
     return SYMGPU_OK;
+}
+
+const char *symgpu_debug_counter_name(int which) {
+    switch (which) {
+#define SG_COUNTER_NAME(name, id, text) case id: return #name;
+        SYMGPU_COUNTER_LIST(SG_COUNTER_NAME)
+#undef SG_COUNTER_NAME
+        default: return nullptr;
+    }
 }
 
 int symgpu_degraded(char *buf, int len) {

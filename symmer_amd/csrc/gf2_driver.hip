@@ -167,10 +167,10 @@ static int read_counters(const Gf2Run &g, const Gf2Switches &sw, i64 *xor_count,
     } else {
         SG_TRY(read_back_words(g.counters.as<u32>(), 6, nullptr, 0, reinterpret_cast<u32 *>(&h)));
     }
-    // which panel the blocks of this run took (symgpu_debug_counter 15 / 16 / 17; a run that is redone after a time-out counts twice)
-    bump_counter(15, (i64)(u32)h.blocks);
-    bump_counter(16, (i64)h.full_panels);
-    bump_counter(17, (i64)(u32)(h.blocks >> 32));
+    // which panel the blocks of this run took (SYMGPU_CTR_GF2_*; a run that is redone after a time-out counts twice)
+    bump_counter(SYMGPU_CTR_GF2_BLOCKS_PANELLED, (i64)(u32)h.blocks);
+    bump_counter(SYMGPU_CTR_GF2_PANEL_FULL_ROWS, (i64)h.full_panels);
+    bump_counter(SYMGPU_CTR_GF2_PANEL_WINDOW, (i64)(u32)(h.blocks >> 32));
     if (sw.debug) fprintf(stderr, "rref %lld x %lld words: full-row panels %u\n", (long long)g.R, (long long)g.Wc, h.full_panels);
     *timed_out = h.timed_out != 0;
     if (!*timed_out && xor_count) *xor_count = (i64)h.xors;

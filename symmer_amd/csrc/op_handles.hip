@@ -153,7 +153,7 @@ int symgpu_op_write(symgpu_op_t op, int64_t row_offset, const uint64_t *rows, co
             HIP_TRY(hipMemcpyAsync(op->coeff + 2 * (size_t)row_offset, coeff, (size_t)count * 16, hipMemcpyHostToDevice, ctx().stream));
         HIP_TRY(hipStreamSynchronize(ctx().stream));
         count_h2d((size_t)count * W * 8 + ((coeff && op->coeff) ? (size_t)count * 16 : 0));
-        bump_counter(9);
+        bump_counter(SYMGPU_CTR_OP_UPLOADS);
     }
     op_invalidate(op);
     if (row_offset + count > op->T) op->T = row_offset + count;
@@ -197,7 +197,7 @@ int symgpu_op_upload(const uint64_t *rows, const double *coeff, int64_t T, int W
         if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);   // host buffers are not retained past the call
         if (e != hipSuccess) return hip_fail(e, "op_upload memcpy", __FILE__, __LINE__);
         count_h2d((size_t)T * 2 * Wq * sizeof(u64) + (coeff ? (size_t)T * 16 : 0));
-        bump_counter(9);
+        bump_counter(SYMGPU_CTR_OP_UPLOADS);
     }
     f.hand_out(out);
     return SYMGPU_OK;
@@ -221,7 +221,7 @@ int symgpu_op_download(symgpu_op_t op, uint64_t *rows, double *coeff, int64_t ca
             HIP_TRY(hipMemcpyAsync(coeff, op->coeff, (size_t)op->T * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
             count_d2h((size_t)op->T * 16);
         }
-        if (rows || coeff) bump_counter(10);
+        if (rows || coeff) bump_counter(SYMGPU_CTR_OP_DOWNLOADS);
     }
     HIP_TRY(hipStreamSynchronize(ctx().stream));
     return SYMGPU_OK;
@@ -251,7 +251,7 @@ int symgpu_op_set_coeff(symgpu_op_t op, const double *coeff_host) {
         HIP_TRY(hipMemcpyAsync(op->coeff, coeff_host, (size_t)op->T * 16, hipMemcpyHostToDevice, ctx().stream));
         HIP_TRY(hipStreamSynchronize(ctx().stream));              // host buffers are not retained past the call
         count_h2d((size_t)op->T * 16);
-        bump_counter(9);
+        bump_counter(SYMGPU_CTR_OP_UPLOADS);
     }
     return SYMGPU_OK;                                             // the rows did not change: per-handle caches stay
 }
@@ -303,7 +303,7 @@ int symgpu_op_upload_bool(const uint8_t *symp, const double *coeff, int64_t T, i
         if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);   // host buffers are not retained past the call (and the staging buffer goes)
         if (e != hipSuccess) return hip_fail(e, "op_upload_bool", __FILE__, __LINE__);
         count_h2d(nb + (coeff ? (size_t)T * 16 : 0));
-        bump_counter(9);
+        bump_counter(SYMGPU_CTR_OP_UPLOADS);
     }
     f.hand_out(out);
     return SYMGPU_OK;
@@ -325,7 +325,7 @@ int symgpu_op_download_bool(symgpu_op_t op, int n_qubits, uint8_t *symp_out, int
     KERNEL_CHECK();
     SG_TRY(download_any(stage.p, symp_out, nb));
     count_d2h(nb);
-    bump_counter(10);
+    bump_counter(SYMGPU_CTR_OP_DOWNLOADS);
     return SYMGPU_OK;
 }
 

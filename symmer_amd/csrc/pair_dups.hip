@@ -83,7 +83,7 @@ __global__ __launch_bounds__(1024) void k_pd_bucket(const u64 *__restrict__ hI, 
     const int per = (nb + 1023) / 1024;                                     // buckets per lane, consecutive
     u32 mine = 0, longest = 0;
     for (int k = 0; k < per; ++k) { const int a = tid * per + k; if (a < nb) { const u32 c = s_cnt[a]; mine += c; longest = c > longest ? c : longest; } }
-    if (longest > (u32)PD_MAX_BUCKET) atomicOr(giveup, 8u);
+    if (longest > (u32)PD_MAX_BUCKET) atomicOr(giveup, PD_GIVEUP_OPERAND_BUCKET);
     const u32 inc = pd_wave_scan(mine);
     if (lane == 63) s_wsum[wave] = inc;
     __syncthreads();
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_pair_dups(const PairDupArgs a) {
     __shared__ __attribute__((aligned(16))) u32 s_wsum[64];                     // inclusive sums per wavefront: pairs, tiles (and the same of the second groups)
     __shared__ u32 s_nc, s_over;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (*a.giveup & 8u) return;                                                 // a bucket longer than the positions below can address: not for this path
+    if (*a.giveup & PD_GIVEUP_OPERAND_BUCKET) return;                           // a bucket longer than the positions below can address: not for this path
     const u32 *s_wO = a.squared ? s_w : s_w + a.nI;
     for (int i = tid; i < nTab; i += NT) s_w[i] = a.tab_w[i];
     for (int i = tid; i < nb + 4; i += NT) {                                    // (padded with the table's length: the groups of four below read one start past theirs)
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_pair_dups(const PairDupArgs a) {
             const u32 P1 = P, ntl1 = ntl;
             P += P2; ntl += ntl2;
             if (P > (u32)(PD_QUOTA * NT)) {                                     // (block-uniform)
-                if (tid == 0) atomicOr(a.giveup, 1u);
+                if (tid == 0) atomicOr(a.giveup, PD_GIVEUP_PRODUCT_BUCKET);
                 __syncthreads();
                 continue;
             }
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_pair_dups(const PairDupArgs a) {
         __syncthreads();
         PD_STAMP(1);
         if (s_over) {                                                           // rows repeated all over
-            if (tid == 0) atomicOr(a.giveup, 2u);
+            if (tid == 0) atomicOr(a.giveup, PD_GIVEUP_COUNTER_SATURATED);
             __syncthreads();
             continue;
         }
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_pair_dups(const PairDupArgs a) {
         PD_STAMP(2);
         const u32 nc = s_nc;
         if (nc > (u32)PD_CAND) {
-            if (tid == 0) atomicOr(a.giveup, 4u);
+            if (tid == 0) atomicOr(a.giveup, PD_GIVEUP_LIST_OVERFLOW);
             __syncthreads();
             continue;
         }

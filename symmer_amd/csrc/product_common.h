@@ -44,6 +44,12 @@ enum class ProductPath {
     WordMajorBesideRows,             // the same on two streams (SYMGPU_PRODUCT_OVERLAP=1, for experiments): it paid while the row stream
                                      // wrote 12 rows per block (6.1 TB/s either way)
 };
+// the counter of the calls a path served (product_driver.hip bumps it at the switch)
+constexpr symgpu_counter counter_of(ProductPath p) { return (symgpu_counter)(SYMGPU_CTR_PRODUCT_ROWS_ONLY + (int)p); }
+static_assert(counter_of(ProductPath::RowsOnly) == SYMGPU_CTR_PRODUCT_ROWS_ONLY && counter_of(ProductPath::PhaseStream) == SYMGPU_CTR_PRODUCT_PHASE_STREAM &&
+              counter_of(ProductPath::WideCoeffThenRows) == SYMGPU_CTR_PRODUCT_WIDE_COEFF_THEN_ROWS &&
+              counter_of(ProductPath::WordMajorThenRows) == SYMGPU_CTR_PRODUCT_WORD_MAJOR_THEN_ROWS &&
+              counter_of(ProductPath::WordMajorBesideRows) == SYMGPU_CTR_PRODUCT_WORD_MAJOR_BESIDE_ROWS, "ProductPath and its counters are in one order");
 
 // What a call decides before it launches anything.  A row stream (plain or phase-byte) covers the inner operand tile by tile and the outer rows
 // in batches of at most MAX_GRID_Y grid.y indices: for_each_piece.

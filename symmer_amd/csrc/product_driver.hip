@@ -152,7 +152,7 @@ int symgpu_mul_allpairs_dev(symgpu_op_t inner, symgpu_op_t outer, int64_t o_begi
         const ProductSwitches sw = read_product_switches();
         const ProductPlan pl = plan_product(inner->T, o_end - o_begin, inner->Wq, out->coeff != nullptr, sw);
         const ProductCall p{inner, outer, out, o_begin, o_end, inner_is_left};
-        bump_counter(48 + (int)pl.path);                  // which path served the call: symgpu_debug_counter 48 .. 52, in ProductPath's order
+        bump_counter(counter_of(pl.path));                // which path served the call
         switch (pl.path) {
             case ProductPath::RowsOnly: SG_TRY(stream_rows(pl, p)); break;
             case ProductPath::PhaseStream: SG_TRY(stream_rows_and_phase_bytes(pl, p)); break;

@@ -233,7 +233,7 @@ static int clifford_chain_registers(symgpu_op_t a, symgpu_op_t b, i64 T, const u
         const int end_bit = CHAIN_IDX_BITS + 8 * ((n + 7) / 8);
         SortResult sorted;
         SG_TRY(radix_sort({knew, ktmp, nullptr, nullptr, T, CHAIN_IDX_BITS, end_bit, nullptr, SortForm::OneLaunchIfFits}, &sorted));     // one launch for all passes up to 2^19 keys
-        bump_counter(sorted.one_launch ? 27 : 28);                                  // (a run that is redone after a time-out counts both)
+        bump_counter(sorted.one_launch ? SYMGPU_CTR_CHAIN_SORT_ONE_LAUNCH : SYMGPU_CTR_CHAIN_SORT_LAUNCHES);                                  // (a run that is redone after a time-out counts both)
         perm = sorted.keys;
         symgpu_op_t t2 = cur; cur = other; other = t2;
     }

@@ -155,6 +155,9 @@ int rotate_general(RotationRun &r);
 // Where the rows of a block stay between the one read and the write: in LDS; in LDS but for two 1,024-chunk rounds of the load that stay in
 // registers; or in memory, read a second time when they are written out (only the 26 bytes of per-row state are in LDS then).
 enum class ResidentForm { Lds, Registers, RowsInMemory };
+constexpr symgpu_counter counter_of(ResidentForm f) { return (symgpu_counter)(SYMGPU_CTR_RESIDENT_LDS + (int)f); }   // launches by form
+static_assert(counter_of(ResidentForm::Lds) == SYMGPU_CTR_RESIDENT_LDS && counter_of(ResidentForm::Registers) == SYMGPU_CTR_RESIDENT_REGISTERS &&
+              counter_of(ResidentForm::RowsInMemory) == SYMGPU_CTR_RESIDENT_ROWS_IN_MEMORY, "ResidentForm and its counters are in one order");
 struct ResidentPlan {
     bool applicable = false;                               // the operator qualifies (what the process state may still veto: rotate_resident_try)
     ResidentForm form = ResidentForm::Lds;

@@ -76,6 +76,10 @@ static RotationPlan plan_rotation(symgpu_op_t in, int clifford_k, const RotateSw
 
 // The form of a run of Clifford rotations (T > 0 rows, K > 0 rotations).
 enum class ChainForm { Registers, Lds, SingleWorkgroup, TwoLaunch, FourLaunch };
+constexpr symgpu_counter counter_of(ChainForm f) { return (symgpu_counter)(SYMGPU_CTR_CHAIN_REGISTERS + (int)f); }   // runs by form
+static_assert(counter_of(ChainForm::Registers) == SYMGPU_CTR_CHAIN_REGISTERS && counter_of(ChainForm::Lds) == SYMGPU_CTR_CHAIN_LDS &&
+              counter_of(ChainForm::SingleWorkgroup) == SYMGPU_CTR_CHAIN_SINGLE_WORKGROUP && counter_of(ChainForm::TwoLaunch) == SYMGPU_CTR_CHAIN_TWO_LAUNCHES &&
+              counter_of(ChainForm::FourLaunch) == SYMGPU_CTR_CHAIN_FOUR_LAUNCHES, "ChainForm and its counters are in one order");
 
 static ChainForm plan_chain(i64 T, int Wq, const RotateSwitches &sw) {
     const int W = 2 * Wq;
@@ -92,9 +96,9 @@ static ChainForm plan_chain(i64 T, int Wq, const RotateSwitches &sw) {
     return ChainForm::FourLaunch;
 }
 
-// which form served the run: symgpu_debug_counter 22 (registers) / 23 (LDS) / 24 (single workgroup) / 25 (two launches) / 26 (four launches)
+// which form served the run is counted here and nowhere else
 static int run_chain(ChainForm form, const ChainRun &c, int *in_b) {
-    bump_counter(22 + (int)form);
+    bump_counter(counter_of(form));
     switch (form) {
         case ChainForm::Registers: return chain_registers(c, in_b);
         case ChainForm::Lds: return chain_lds(c, in_b);
@@ -172,22 +176,22 @@ int symgpu_rotate_single_dev(symgpu_op_t in, const uint64_t *q_row_host, double 
     // exactly one analysis launch; Q reaches the device with it (in its kernel arguments when the row has <= 64 words)
     if (pl.join) {
         SG_TRY(rotate_join(r, &done));
-        if (done) { bump_counter(29); return SYMGPU_OK; }            // else duplicate rows: the general stage
+        if (done) { bump_counter(SYMGPU_CTR_ROTATE_HASH_JOIN); return SYMGPU_OK; }            // else duplicate rows: the general stage
     } else if (pl.dup_check) {
         SG_TRY(rotate_dup_check(r));
     } else {
         SG_TRY(analyze_rows(in, r.q.as<u64>(), r.anti.as<u32>(), r.ph.as<uint8_t>(), nullptr, sw, q_row_host));
     }
-    // the stage that completed the rotation: symgpu_debug_counter 29 (hash join, above) / 30 (Clifford fast path) / 31 (general path), 32: of
-    // 31, the rotations whose duplicate check found two equal rows (the one-launch kernel counts its own: 1)
+    // the stage that completed the rotation is counted: the hash join above, the Clifford fast path, the general path, and of the last
+    // the rotations whose duplicate check found two equal rows (the one-launch kernel counts its own: SYMGPU_CTR_RESIDENT_DONE)
     if (pl.clifford_fast && !r.has_dup) {
         SG_TRY(rotate_clifford_fast(r));
-        bump_counter(30);
+        bump_counter(SYMGPU_CTR_ROTATE_CLIFFORD_FAST);
         return SYMGPU_OK;
     }
     SG_TRY(rotate_general(r));
-    bump_counter(31);
-    if (pl.dup_check && r.has_dup) bump_counter(32);
+    bump_counter(SYMGPU_CTR_ROTATE_GENERAL);
+    if (pl.dup_check && r.has_dup) bump_counter(SYMGPU_CTR_ROTATE_GENERAL_BY_DUP_CHECK);
     return SYMGPU_OK;
 }
 

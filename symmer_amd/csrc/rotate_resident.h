@@ -71,7 +71,7 @@ struct ResArgs {
 
 // rotate_resident_kernel.hip
 bool resident_lds_attr_ok();                      // k_rot_resident may use RES_LDS_MAX of LDS (once per device)
-// the one launch of a planned call; which form it was: symgpu_debug_counter 33 (LDS) / 34 (registers) / 35 (rows in memory), here and nowhere else
+// the one launch of a planned call; which form it was is counted (counter_of(ResidentForm)) here and nowhere else
 hipError_t launch_resident(const ResidentPlan &p, bool clifford, hipStream_t st, const ResArgs &a);
 
 }  // namespace symgpu

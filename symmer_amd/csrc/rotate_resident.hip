@@ -168,7 +168,7 @@ static hipError_t await_report(hipStream_t st, const volatile u64 *host_words, u
 static int finish(ResidentState &s, const RotCounts &hc, symgpu_op_t in, bool clifford, symgpu_op_t res, symgpu_op_t *out, int *all_commute, int *done) {
     if (hc.dup != 0) {                                                             // verification failed (2), timed out (3), or no report at all (1)
         symgpu_op_free(res);
-        bump_counter(2);
+        bump_counter(SYMGPU_CTR_RESIDENT_FAILED);
         if (hc.dup != 2) {                                                         // time-out: arrival counts are in an unknown state
             s.disabled = true; s.epoch = 0;
             note_degraded("one-launch rotation (k_rot_resident) off: an in-kernel wait timed out (workgroups not co-resident?); rotations take the multi-launch kernels");
@@ -179,7 +179,7 @@ static int finish(ResidentState &s, const RotCounts &hc, symgpu_op_t in, bool cl
         return SYMGPU_OK;
     }
     *done = 1;
-    bump_counter(1);
+    bump_counter(SYMGPU_CTR_RESIDENT_DONE);
     if (hc.nAnti == 0) { symgpu_op_free(res); *all_commute = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133)
     res->T = (i64)hc.nC + hc.nA + hc.nN;
     res->dup_free = clifford ? in->dup_free : 1;
@@ -235,11 +235,11 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
     const i64 t_launch = host_ns();
     hipError_t e = launch_resident(plan, clifford, st, a);
     const i64 t_wait = host_ns();
-    bump_counter(4, t_launch - t_enter); bump_counter(5, t_wait - t_launch);
+    bump_counter(SYMGPU_CTR_RESIDENT_NS_PREPARE, t_launch - t_enter); bump_counter(SYMGPU_CTR_RESIDENT_NS_LAUNCH, t_wait - t_launch);
     RotCounts hc;
     if (e == hipSuccess) e = await_report(st, host_words, s.host_tag, &hc);
     if (e != hipSuccess) { symgpu_op_free(res); s.dirty = true; return hip_fail(e, "rotate resident", __FILE__, __LINE__); }
-    bump_counter(6, host_ns() - t_wait);
+    bump_counter(SYMGPU_CTR_RESIDENT_NS_WAIT, host_ns() - t_wait);
     return finish(s, hc, in, clifford, res, out, all_commute, done);
 }
 

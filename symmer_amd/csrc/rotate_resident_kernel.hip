@@ -644,7 +644,7 @@ bool resident_lds_attr_ok() {
 }
 
 hipError_t launch_resident(const ResidentPlan &p, bool clifford, hipStream_t st, const ResArgs &a) {
-    bump_counter(33 + (int)p.form);
+    bump_counter(counter_of(p.form));
     {
         ProfScope prof(4);
         hipLaunchKernelGGL(res_kernel(clifford, a.Wq), dim3((unsigned)p.G), dim3(RES_THREADS), (size_t)p.lds_bytes, st, a);

@@ -428,7 +428,7 @@ static int csr_fill_launch(const symgpu_csr_s *p, const CsrFillForm &f, f64x2 *d
             hipLaunchKernelGGL((k_csr_fill<true, IDX>), dim3((unsigned)nb), dim3(CSR_WG), 0, st, P, f.RB, b0, (const u64 *)p->indptr, p->nnz,
                                slots.as<char>(), data, indices);
         KERNEL_CHECK();
-        bump_counter(f.lds ? 53 : 54);                     // symgpu_debug_counter 53 / 54: launches of the fill by form, here and nowhere else
+        bump_counter(f.lds ? SYMGPU_CTR_CSR_FILL_LDS : SYMGPU_CTR_CSR_FILL_SCRATCH);   // launches of the fill by form, here and nowhere else
     }
     return SYMGPU_OK;
 }

@@ -182,14 +182,21 @@ def slice_dev(op, begin, end, with_coeff=True):
     return out
 
 
+def counter(name):
+    """The library's debug counter `name` (as spelled in SYMGPU_COUNTER_LIST of include/symgpu.h, e.g. 'H2D_BYTES'); KeyError if there is none."""
+    v = c_i64(0)
+    check(_lib.load().symgpu_debug_counter(_lib.counter_ids()[name], ctypes.addressof(v)))   # (needs no device)
+    return v.value
+
+
+def counters(names):
+    """The debug counters `names`, in that order, as an int64 array."""
+    return np.array([counter(name) for name in names], dtype=np.int64)
+
+
 def transfer_counters():
     """(bytes host -> device, bytes device -> host, operator uploads, operator downloads) since the library was loaded."""
-    v = c_i64(0)
-    out = []
-    for which in (7, 8, 9, 10):
-        check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-        out.append(v.value)
-    return tuple(out)
+    return tuple(int(v) for v in counters(('H2D_BYTES', 'D2H_BYTES', 'OP_UPLOADS', 'OP_DOWNLOADS')))
 
 
 def sync():

@@ -361,15 +361,13 @@ def flow_name(pl):
     return f"hash-table flag pass B = {pl['direct'][0]}" + (', 16-bit counters' if pl['direct'][1] == 16 else '') + (', bytes' if pl['key_bytes'] else ', keys')
 
 
-# symgpu_debug_counter 36 .. 47 (include/symgpu.h)
-FLOW_COUNTERS = ('complete sort', 'flag pass from the hash tables', 'flag pass behind the partial sort', 'flag pass gave up',
-                 'reason: product bucket over 16,384 pairs', 'reason: counter saturated', 'reason: list overflow', 'reason: operand bucket over 255',
-                 'whole array sorted after the flag pass', 'flagged keys sorted alone', 'singles marked from bytes', 'repeated with the full 64-bit sort')
+# the counters of the product + cleanup flows, by name (SYMGPU_COUNTER_LIST of include/symgpu.h), in id order; C_* index this tuple
+FLOW_COUNTERS = ('FLOW_COMPLETE_SORT', 'FLOW_FLAGS_HASH_TABLES', 'FLOW_FLAGS_PARTIAL_SORT', 'FLOW_FLAGS_GAVE_UP',
+                 'GIVEUP_PRODUCT_BUCKET', 'GIVEUP_COUNTER_SATURATED', 'GIVEUP_LIST_OVERFLOW', 'GIVEUP_OPERAND_BUCKET',
+                 'FLOW_SORTED_WHOLE', 'FLOW_SORTED_FLAGGED', 'FLOW_MARKED_FROM_BYTES', 'FLOW_FULL_SORT_REPEAT')
 C_FULL, C_DIRECT, C_SORTED, C_GIVEUP, C_R_BUCKET, C_R_SAT, C_R_LIST, C_R_OPERAND, C_WHOLE, C_ALONE, C_BYTES, C_REPEAT = range(12)
-FIRST_FLOW_COUNTER = 36
-# symgpu_debug_counter 48 .. 52: ProductPath of product_common.h
+# ProductPath of product_common.h, in the enum's order (its counters: PRODUCT_* of the same list)
 PRODUCT_PATHS = ('rows only', 'phase stream', 'wide coefficients, then rows', 'word-major coefficients, then rows', 'word-major coefficients beside rows')
-FIRST_PRODUCT_COUNTER = 48
 
 
 def expected_counters(pl, outcome='alone', reasons=()):

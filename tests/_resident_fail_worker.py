@@ -1,24 +1,19 @@
 # fresh process: the one-launch rotation kernel must report what it cannot do exactly, and the caller must still get the right result.
 #   weakhash: SYMGPU_HASH_WEAK_ODD=1 keeps 4 bits of the row hash -> distinct rows with equal hashes -> verification failure (code 2)
 #   timeout : SYMGPU_ROT_RESIDENT=3 lets one workgroup leave without a word -> the all-gather times out (code 3), the path is switched off
-import os, sys, ctypes
+import os, sys
 mode = sys.argv[1]
 if mode == 'weakhash':
     os.environ['SYMGPU_HASH_WEAK_ODD'] = '1'
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from symmer_amd import _lib, kernels, packing
+from symmer_amd import kernels, packing
 from symmer_amd.kernels import DeviceOp
 from oracle import oracle_np as onp
 
 
-def counter(which):
-    v = ctypes.c_int64(-1)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
-
-
+done, failed = (lambda: kernels.counter('RESIDENT_DONE')), (lambda: kernels.counter('RESIDENT_FAILED'))
 rng = np.random.default_rng(41)
 dy = lambda t: (rng.integers(-8, 9, t) + 1j * rng.integers(-8, 9, t)) / 16.0
 n, T = 200, 4000
@@ -30,11 +25,11 @@ qp = packing.pack_rows(q.reshape(1, -1))[0]
 op = DeviceOp.upload(packing.pack_rows(symp), c)
 first, _ = kernels.rotate_single_dev(op, qp, 0.7)               # multi-launch path: duplicate status and hashes of `op`
 first.free()
-assert counter(1) == 0 and counter(2) == 0
+assert done() == 0 and failed() == 0
 if mode == 'timeout':
     os.environ['SYMGPU_ROT_RESIDENT'] = '3'
 res, allc = kernels.rotate_single_dev(op, qp, 0.3)
-assert counter(2) == 1 and counter(1) == 0, (counter(1), counter(2))
+assert failed() == 1 and done() == 0, (done(), failed())
 rows, coeff = res.download()
 er, ec = onp.rotate_by_single_pword(symp, c, q, 0.3)
 kd, ko = np.abs(coeff) > 1e-12, np.abs(ec) > 1e-12
@@ -44,10 +39,10 @@ if mode == 'timeout':
     assert any('k_rot_resident' in t for t in _l.degraded()), _l.degraded()     # a lost fast path is visible (stderr once + symgpu_degraded)
     os.environ.pop('SYMGPU_ROT_RESIDENT')
     r2, _ = kernels.rotate_single_dev(op, qp, 0.3)             # switched off after a time-out: multi-launch path, no new attempt
-    assert counter(2) == 1 and counter(1) == 0
+    assert failed() == 1 and done() == 0
     os.environ['SYMGPU_ROT_RESIDENT'] = '2'                     # ... until it is asked for again
     r3, _ = kernels.rotate_single_dev(op, qp, 0.3)
-    assert counter(1) == 1, counter(1)
+    assert done() == 1, done()
     a, b = r2.download(), r3.download()
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 print('RESIDENT_FAIL_OK', flush=True)

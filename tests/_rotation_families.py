@@ -338,6 +338,7 @@ def long_run(n, T, K, rng, fourfold=False, q_words=None, step=table_step):
 
 # ---------------------------------------------------------------- the plan, restated ------------------------------------------------------
 FORMS = ('Registers', 'Lds', 'SingleWorkgroup', 'TwoLaunch', 'FourLaunch')
+FORM_COUNTERS = ('CHAIN_REGISTERS', 'CHAIN_LDS', 'CHAIN_SINGLE_WORKGROUP', 'CHAIN_TWO_LAUNCHES', 'CHAIN_FOUR_LAUNCHES')   # the counter of each form
 
 
 def header_constants(text):
@@ -377,7 +378,8 @@ def register_chunks(T, wq):
 
 
 # ---------------------------------------------------------------- the one-launch rotation's plan, restated --------------------------------
-RES_FORMS = ('Lds', 'Registers', 'RowsInMemory')                      # ResidentForm of rotate_common.h; symgpu_debug_counter 33 / 34 / 35
+RES_FORMS = ('Lds', 'Registers', 'RowsInMemory')                      # ResidentForm of rotate_common.h
+RES_FORM_COUNTERS = ('RESIDENT_LDS', 'RESIDENT_REGISTERS', 'RESIDENT_ROWS_IN_MEMORY')   # the counter of each form
 RES_NAMES = ('RES_THREADS', 'RES_MAX_WG', 'RES_LDS_MAX', 'RES_MIN_ROWS', 'RES_MAX_R', 'RES_REG_ROUNDS', 'RES_REG_MAX_WQ', 'RES_MAX_W', 'JOIN_MAX_T')
 
 
@@ -449,13 +451,10 @@ def device_cu_count():
     return int(m.group(1))
 
 
+RESIDENT_COUNTERS = ('RESIDENT_DONE', 'RESIDENT_FAILED') + RES_FORM_COUNTERS
+
+
 def resident_counters():
-    """symgpu_debug_counter [1, 2, 33, 34, 35]: one-launch rotations completed, failed, and launched in the LDS / registers / rows-in-memory form."""
-    import ctypes
-    from symmer_amd import _lib
-    v = ctypes.c_int64(-1)
-    out = []
-    for which in (1, 2, 33, 34, 35):
-        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-        out.append(v.value)
-    return np.array(out)
+    """RESIDENT_COUNTERS: one-launch rotations completed, failed, and launched in the LDS / registers / rows-in-memory form."""
+    from symmer_amd import kernels
+    return kernels.counters(RESIDENT_COUNTERS)

@@ -1,17 +1,14 @@
 # fresh process, SYMGPU_HASH_WEAK_ODD=1: the first hash seed (1, odd) keeps only 4 hash bits, so different rows collide in bulk.
 # The cleanup must notice (row-against-row verification), reseed (seed 2: full hash) and still return the oracle's result.
-import os, sys, ctypes
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from symmer_amd import PauliwordOp, _lib
+from symmer_amd import PauliwordOp, kernels
 from oracle import oracle_np as onp
 from _golden import assert_op_equal
 
-def reseeds():
-    v = ctypes.c_int64(-1)
-    _lib.check(_lib.lib().symgpu_debug_counter(0, ctypes.addressof(v)))
-    return v.value
+reseeds = lambda: kernels.counter('HASH_RESEEDS')
 
 rng = np.random.default_rng(31)
 dy = lambda t: (rng.integers(-8, 9, t) + 1j * rng.integers(-8, 9, t)) / 16.0

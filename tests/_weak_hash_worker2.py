@@ -1,10 +1,10 @@
 # as _weak_hash_worker.py, but the FIRST cleanup of the process is a fused product + cleanup (packed pair keys, squared operator),
 # then a rotation on weak hashes: every path that consumes row hashes meets bulk collisions once.
-import os, sys, ctypes
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from symmer_amd import PauliwordOp, _lib
+from symmer_amd import PauliwordOp, kernels
 from oracle import oracle_np as onp
 from _golden import assert_op_equal
 mode = sys.argv[1]
@@ -21,10 +21,10 @@ if mode in ('square', 'pair'):
     es, ec = onp.mul(X.symp_matrix, X.coeff_vec, Y.symp_matrix, Y.coeff_vec)
     assert np.array_equal(R.symp_matrix, es) and np.array_equal(R.coeff_vec, ec)
     # 4,000 / 3,240 keys in 16 hash classes are runs of hundreds of equal sorted prefixes that hold different keys: the attempt must have been
-    # repeated with the full 64-bit sort (symgpu_debug_counter 47) before the collisions forced the reseed
-    w = ctypes.c_int64(-1); _lib.check(_lib.lib().symgpu_debug_counter(47, ctypes.addressof(w)))
-    print('full-sort repeats', w.value, flush=True)
-    assert w.value >= 1, 'long mixed prefix runs did not send the attempt to the full 64-bit sort'
+    # repeated with the full 64-bit sort (FLOW_FULL_SORT_REPEAT) before the collisions forced the reseed
+    w = kernels.counter('FLOW_FULL_SORT_REPEAT')
+    print('full-sort repeats', w, flush=True)
+    assert w >= 1, 'long mixed prefix runs did not send the attempt to the full 64-bit sort'
 else:                                                                      # rotation first: hash join on weak hashes (seed 1)
     symp, c = onp.cleanup_op(np.vstack([A.symp_matrix, B.symp_matrix]), np.hstack([A.coeff_vec, B.coeff_vec]))
     q = rng.random(2 * n) < 0.3
@@ -35,6 +35,6 @@ else:                                                                      # rot
         R = P._rotate_by_single_Pword(PauliwordOp(q.reshape(1, -1), [1]), ang)
         er, ec = onp.rotate_by_single_pword(symp, c, q, ang)
         assert_op_equal(R.symp_matrix, R.coeff_vec, er, ec, exact=ang != 0.3, tol=1e-12)
-v = ctypes.c_int64(-1); _lib.check(_lib.lib().symgpu_debug_counter(0, ctypes.addressof(v)))
-assert mode == 'rotate' or v.value >= 1, 'the weak first seed must have forced a reseed'   # the hash join itself verifies rows on every tag hit
-print('WEAK_HASH_OK', mode, v.value, flush=True)
+v = kernels.counter('HASH_RESEEDS')
+assert mode == 'rotate' or v >= 1, 'the weak first seed must have forced a reseed'   # the hash join itself verifies rows on every tag hit
+print('WEAK_HASH_OK', mode, v, flush=True)

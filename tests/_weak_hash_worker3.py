@@ -6,11 +6,11 @@
 #                  result duplicate free.  500 x 3000 rows in 16 hash classes: every probe walks rows that are different with equal hashes.
 #   noncontextual  T = 1000: the True operator first (wrongly merged characters would lose set bits and answer False), then a bridge as last term
 #   project        70,000 terms collapsing onto at most 64 rows: the cleanup behind the projection on colliding hashes
-import os, sys, ctypes
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from symmer_amd import PauliwordOp, kernels, packing, _lib
+from symmer_amd import PauliwordOp, kernels, packing
 from symmer_amd.kernels import DeviceOp
 from oracle import oracle_np as onp
 import _f3_f4_families as fam
@@ -19,9 +19,7 @@ mode = sys.argv[1]
 
 
 def reseeds():
-    v = ctypes.c_int64(-1)
-    _lib.check(_lib.lib().symgpu_debug_counter(0, ctypes.addressof(v)))
-    return v.value
+    return kernels.counter('HASH_RESEEDS')
 
 
 if mode == 'inner':

@@ -3,19 +3,17 @@
 # collision reseeds to the full hash and the table would never see the weak one): rows uploaded, indexed 0..S-1 and passed through
 # symgpu_merge_indexed_dev without cleanup, which orders by index (no hash) and marks its result duplicate free.  S = 300 basis strings and T = 64
 # terms in 16 hash classes: every probe walks rows that are different with equal hashes; dyadic amplitudes, so the answer is exact.  Both forms.
-import os, sys, ctypes
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from symmer_amd import kernels, packing, _lib
+from symmer_amd import kernels, packing
 from symmer_amd.kernels import DeviceOp
 import _expval_oracle as ora
 
 
 def reseeds():
-    v = ctypes.c_int64(-1)
-    _lib.check(_lib.lib().symgpu_debug_counter(0, ctypes.addressof(v)))
-    return v.value
+    return kernels.counter('HASH_RESEEDS')
 
 
 def unhashed_state(bits, amp):

@@ -7,11 +7,10 @@ Coefficients are compared as bits: signed zeros included, NaN positions equal (a
 operation creates is negative on x86-64 and positive on the GPU).  Where the device's product rule (the plain, unfused
 product, the phase applied exactly) does not give NumPy's FMA product bit for bit — non-finite factors, general inexact coefficients; the
 fixture's ``exact`` flag — products are compared with the C oracle, which states that rule, and rotations path against path."""
-import ctypes
 
 import numpy as np
 import pytest
-from symmer_amd import PauliwordOp, kernels, _lib
+from symmer_amd import PauliwordOp, kernels
 from oracle import oracle_np as onp
 from oracle import oracle_c as oc
 from _golden import family, as_bool
@@ -148,7 +147,7 @@ def test_rotation_edges(case, path, monkeypatch):
     cs, cc = onp.cleanup_op(us, uc)
     R = PauliwordOp(us, uc).cleanup()._rotate_by_single_Pword(Q, ang)
     assert_bits(R.symp_matrix, R.coeff_vec, *onp.rotate_by_single_pword(cs, cc, q, ang), what=path + ', after cleanup', zero_sign=zs)
-    # the form of every one-launch rotation above (symgpu_debug_counter 33 / 34 / 35 against 1 + 2): rows in LDS at these sizes, left in
+    # the form of every one-launch rotation above (fam.RESIDENT_COUNTERS: the three forms against done + failed): rows in LDS at these sizes, left in
     # memory where that is forced, none on the general path; the cleaned operator's rotation is one of them
     done, failed, lds, regs, mem = fam.resident_counters() - forms_before
     assert [lds, regs, mem] == {'resident': [done + failed, 0, 0], 'general': [0, 0, 0], 'rows in memory': [0, 0, done + failed]}[path], (path, done, failed, lds, regs, mem)
@@ -178,23 +177,13 @@ def _edges(thr):
                      complex(2.2e-308, -1e-310)])
 
 
-def _counter(which):
-    v = ctypes.c_int64(0)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
-
-
-def _flow_counters():
-    return np.array([_counter(pfam.FIRST_FLOW_COUNTER + k) for k in range(len(pfam.FLOW_COUNTERS))])
-
-
 @pytest.mark.parametrize('path', [p for p in MUL_PATHS if p != 'no square'])
 def test_gated_product_edges(path, monkeypatch):
     """Above the 2^22-key gate (the shapes of test_gpu_fullsize: 100 qubits, 2600 x 2100 terms — the flag pass, the lazy flow): edge
     coefficients in the inner operand against outer coefficients 1, -1, i and 0.5 (exact products at the threshold), and the coefficient
     floor shortcut (all operand components non-zero: every pair kept unseen) switched off by one term (inf, inf) against a term (1, 0),
     whose plain product is (NaN, NaN).
-    Every call took the flow its mode is named for (symgpu_debug_counter 36 .. 47 against the restated plan): by default the flag pass from
+    Every call took the flow its mode is named for (the counters pfam.FLOW_COUNTERS against the restated plan): by default the flag pass from
     the operand hash tables (512 product buckets) with marking from bytes, the flagged keys sorted alone; 'sorted flag pass' the pass behind the
     partial sort; 'key words' the hash-table pass without the bytes; 'give up' the whole array sorted behind a flag pass that did NOT give up;
     'full sort' and 'lazy off' the complete sort; 'unpacked' none of them."""
@@ -213,10 +202,10 @@ def test_gated_product_edges(path, monkeypatch):
             ca[1234] = complex(np.inf, np.inf); cb[7] = 1.0
         A, B = onp.pack_rows(sa), onp.pack_rows(sb)
         pl = pfam.plan_cleanup(na, nb, False, thr, **MUL_PLAN[path])
-        reseeds, before = _counter(0), _flow_counters()
+        reseeds, before = kernels.counter('HASH_RESEEDS'), kernels.counters(pfam.FLOW_COUNTERS)
         rows, c = kernels.mul_cleanup(A, ca, B, cb, True, thr)
-        took = (_flow_counters() - before).tolist()
-        if reseeds == 0 and _counter(0) == 0:
+        took = (kernels.counters(pfam.FLOW_COUNTERS) - before).tolist()
+        if reseeds == 0 and kernels.counter('HASH_RESEEDS') == 0:
             assert took[:pfam.C_REPEAT] == pfam.expected_counters(pl, 'whole' if path == 'give up' else 'alone')[:pfam.C_REPEAT], (path, plant, pfam.flow_name(pl), dict(zip(pfam.FLOW_COUNTERS, took)))
         er, ec = oc.mul(A, ca, B, cb, thr)
         assert rows.shape[0] > (1 << 21)

@@ -1,10 +1,10 @@
 """GPU: every commutation kernel (csrc/commute.hip, commute_m4r.hip, commute_m4r7.hip, the wide-row path of wide.hip; the path of a call is
 planned in commute_driver.hip) on operands whose
 tables hold BY CONSTRUCTION (tests/_commute_families.py; tests/test_commute_families.py proves the answers against the NumPy oracle on the
-CPU), bit for bit, with the path each call took asserted through symgpu_debug_counter 18-21:
+CPU), bit for bit, with the path each call took asserted through the debug counters (kernels.counters):
 
-  18  calls served by the register-tile kernel          20  Four-Russians launches with one tile per workgroup
-  19  calls served by the wide-row kernel                21  Four-Russians stream-K launches
+  COMMUTE_REGISTER_TILE  calls served by the register-tile kernel     COMMUTE_M4R_TILE     Four-Russians launches with one tile per workgroup
+  COMMUTE_WIDE_ROWS      calls served by the wide-row kernel           COMMUTE_M4R_STREAMK  Four-Russians stream-K launches
 
 What the families pin that dense random operands leave inside random sums:
   one_hot         one contraction bit a row — every pairing "bit c of the left operand with bit c +- 64 Wq of the right one", the 7-bit
@@ -27,7 +27,8 @@ import _commute_families as fam
 pytestmark = pytest.mark.gpu
 
 ENV_NAMES = ('SYMGPU_COMMUTE_M4R', 'SYMGPU_M4R_R', 'SYMGPU_WIDE', 'SYMGPU_M4R_STREAM', 'SYMGPU_M4R_FIXUP', 'SYMGPU_M4R_UNFUSED')
-PATHS = ('register tile', 'wide rows', 'Four-Russians, one tile per workgroup', 'Four-Russians, stream-K')      # counters 18, 19, 20, 21
+PATHS = ('register tile', 'wide rows', 'Four-Russians, one tile per workgroup', 'Four-Russians, stream-K')
+PATH_COUNTERS = ('COMMUTE_REGISTER_TILE', 'COMMUTE_WIDE_ROWS', 'COMMUTE_M4R_TILE', 'COMMUTE_M4R_STREAMK')    # the counter of each path
 TILE, WIDE, M4R_ONE, M4R_STREAM = 0, 1, 2, 3
 # forced kernel -> (switches, the path that must have served the call)
 KERNELS = {
@@ -47,12 +48,7 @@ def set_switches(monkeypatch, env):
 
 
 def counters():
-    v = ctypes.c_int64(0)
-    out = []
-    for which in (18, 19, 20, 21):
-        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-        out.append(v.value)
-    return np.array(out)
+    return kernels.counters(PATH_COUNTERS)
 
 
 def counted(call, path, what):
@@ -335,7 +331,7 @@ def test_sparse_groups_stream_k(r, S, mode, monkeypatch):
     S steps over the persistent workgroups — S = 1 splits no tile, S = 2 and 3 split tiles after their first or second step; `stream`: the
     owner of a tile's first steps adds the neighbour's published part, `fixup` (SYMGPU_M4R_FIXUP=1): both parts go to scratch and
     k_m7_fixup writes the tile.  Bit-packed output, EVERY bit compared with the by-construction table.  The launch must have been a
-    stream-K launch (counter 21): fewer tiles than compute units would silently run one tile per workgroup."""
+    stream-K launch (COMMUTE_M4R_STREAMK): fewer tiles than compute units would silently run one tile per workgroup."""
     a, b, c_bits = stream_case(r, S)
     set_switches(monkeypatch, stream_switches(r, mode))
     A, B = DeviceOp.upload(a), DeviceOp.upload(b)
@@ -474,7 +470,7 @@ def test_cached_bit_major_copy_follows_the_rows(monkeypatch):
 # ---------------------------------------------------------------- 7. the plan: precedence of the switches, read on every call --------------
 def test_forcing_four_russians_beats_the_wide_kernel(monkeypatch):
     """2 x 2 pairs of rows of 256 words a half (n = 16,384) take the wide-row kernel by themselves; SYMGPU_COMMUTE_M4R=1 comes first in the
-    plan: a Four-Russians launch (counter 20) and no wide-row call (counter 19)."""
+    plan: a Four-Russians launch (COMMUTE_M4R_TILE) and no wide-row call (COMMUTE_WIDE_ROWS)."""
     n = 16384
     cols = np.array([64, n + 16383])
     A_, B_, _ = fam.one_hot(n, 2, np.random.default_rng(70), cols=cols)
@@ -504,7 +500,7 @@ def plan_case():
 
 def test_stream_asked_for_but_not_possible(monkeypatch):
     """SYMGPU_M4R_STREAM=1 on 256 x 1024 terms at n = 100: one tile, fewer than compute units, so the launch is one tile per workgroup
-    (counter 20, not 21) and the table is the oracle's."""
+    (COMMUTE_M4R_TILE, not COMMUTE_M4R_STREAMK) and the table is the oracle's."""
     a, b, C = plan_case()
     set_switches(monkeypatch, {'SYMGPU_COMMUTE_M4R': '1', 'SYMGPU_M4R_STREAM': '1'})
     A, B = DeviceOp.upload(a), DeviceOp.upload(b)

@@ -1,6 +1,6 @@
 """PauliwordOp.to_sparse_matrix on the device (csrc/sparse_matrix.hip) on the families of tests/_csr_families.py: every case with int32
 and with int64 indices, in the fill form the library chooses and in the forced global-scratch form, bit for bit against the NumPy
-restatement (tests/_sparse_oracle.py); which form ran, and in how many launches, through symgpu_debug_counter 53 / 54 and the scratch
+restatement (tests/_sparse_oracle.py); which form ran, and in how many launches, through the counters CSR_FILL_LDS / CSR_FILL_SCRATCH and the scratch
 size that the count call reports.  tests/test_csr_families.py proves what each family is."""
 import ctypes
 import functools
@@ -14,7 +14,7 @@ from symmer_amd import PauliwordOp, kernels, _lib
 
 pytestmark = pytest.mark.gpu
 
-FILL_LDS, FILL_SCRATCH = 53, 54              # symgpu_debug_counter: launches of k_csr_fill by form
+FILL_COUNTERS = ('CSR_FILL_LDS', 'CSR_FILL_SCRATCH')     # launches of k_csr_fill by form
 
 BUILDERS = {'x_parts': fam.x_part_set, 'tiles': fam.term_tiles, 'large_n': fam.large_n, 'coeff': fam.coeff_kind}
 CASES = ([('x_parts', D) for D in fam.X_PART_COUNTS] + [('tiles', T) for T in sorted(fam.TERM_TILE_SIZES)]
@@ -30,12 +30,6 @@ def case(family, arg):
     for a in (symp, c) + want:
         a.setflags(write=False)
     return symp, c, facts, want
-
-
-def counter(which):
-    v = ctypes.c_int64(0)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
 
 
 def fill_scratch_bytes(op, n):
@@ -72,9 +66,9 @@ def expected_launches(op, facts, forced_scratch):
 
 
 def run(op, facts, dtype):
-    before = counter(FILL_LDS), counter(FILL_SCRATCH)
+    before = kernels.counters(FILL_COUNTERS)
     got = kernels.to_csr(op._device(), facts['n'], index_dtype=dtype)
-    return got, (counter(FILL_LDS) - before[0], counter(FILL_SCRATCH) - before[1])
+    return got, tuple((kernels.counters(FILL_COUNTERS) - before).tolist())
 
 
 # ---- every family, both index widths, both forms ----------------------------------------------------------------------------------
@@ -155,11 +149,11 @@ def test_memory_refusal_releases_the_plan(monkeypatch):
     op = PauliwordOp(symp.copy(), c.copy())
     dev = op._device()
     monkeypatch.setattr(kernels, '_host_available_bytes', lambda: 1)
-    before = counter(FILL_LDS), counter(FILL_SCRATCH)
+    before = kernels.counters(FILL_COUNTERS)
     for dtype in (None, np.int64):
         with pytest.raises(MemoryError, match='on the host'):
             kernels.to_csr(dev, facts['n'], index_dtype=dtype)
-    assert (counter(FILL_LDS), counter(FILL_SCRATCH)) == before, 'a refused call launched its fill'
+    assert np.array_equal(kernels.counters(FILL_COUNTERS), before), 'a refused call launched its fill'
     monkeypatch.undo()
     assert_bit_equal(kernels.to_csr(dev, facts['n']), want, np.int32)
     assert_bit_equal(kernels.to_csr(dev, facts['n'], index_dtype=np.int64), want, np.int64)

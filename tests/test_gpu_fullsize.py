@@ -228,11 +228,7 @@ def test_cfg2_full_size_rotations_against_the_oracle():
     P.free()
     rows0, c0 = clean.download()
     symp0 = packing.unpack_rows(rows0, n)
-    cnt = ctypes.c_int64(0)
-
-    def one_launch_count():
-        _lib.check(_lib.lib().symgpu_debug_counter(1, ctypes.addressof(cnt)))
-        return cnt.value
+    one_launch_count = lambda: kernels.counter('RESIDENT_DONE')
 
     import _rotation_families as fam
     res_c, cus = fam.resident_constants(fam.resident_header_text()), fam.device_cu_count()
@@ -242,7 +238,7 @@ def test_cfg2_full_size_rotations_against_the_oracle():
         res, allc = kernels.rotate_single_dev(dev_in, qpk, ang)
         assert not allc
         took = one_launch_count() - before
-        # the residency form of the launch (symgpu_debug_counter 33 / 34 / 35) is the one the restated plan gives for this device
+        # the residency form of the launch (fam.RES_FORM_COUNTERS) is the one the restated plan gives for this device
         planned = fam.plan_resident(symp_in.shape[0], fam.wq_of(n), res_c, num_cu=cus)
         assert list(fam.resident_counters()[2:] - forms_before) == [int(planned is not None and planned[0] == f) for f in fam.RES_FORMS], planned
         r, c = res.download()
@@ -265,7 +261,7 @@ def test_cfg2_full_size_rotations_against_the_oracle():
     res3, er3, _, took3 = check(res1, er1, ec1, qs[2], qp[2], -1.1, False)
     assert took3 == 1, 'the register-spill form of the one-launch kernel did not take the 150,000-term operator'
     planned3 = fam.plan_resident(er1.shape[0], fam.wq_of(n), res_c, num_cu=cus)
-    assert cus < 256 or planned3[0] == 'Registers', planned3       # (check() has compared the plan with counter 34)
+    assert cus < 256 or planned3[0] == 'Registers', planned3       # (check() has compared the plan with RESIDENT_REGISTERS)
     assert res3.n_terms > 2.1 * N
     for h in (res1, res3, clean):
         h.free()
@@ -289,17 +285,13 @@ def test_one_launch_rotation_with_the_rows_left_in_memory(n, N, monkeypatch):
     P.free()
     rows0, c0 = clean.download()
     symp0 = packing.unpack_rows(rows0, n)
-    cnt = ctypes.c_int64(0)
-
-    def one_launch_count():
-        _lib.check(_lib.lib().symgpu_debug_counter(1, ctypes.addressof(cnt)))
-        return cnt.value
+    one_launch_count = lambda: kernels.counter('RESIDENT_DONE')
 
     import _rotation_families as fam
     res_c, cus = fam.resident_constants(fam.resident_header_text()), fam.device_cu_count()
 
     def form_launched(T, forms_before):
-        """the launch since `forms_before` had the residency form (symgpu_debug_counter 33 / 34 / 35) of the restated plan for this device"""
+        """the launch since `forms_before` had the residency form (fam.RES_FORM_COUNTERS) of the restated plan for this device"""
         planned = fam.plan_resident(T, fam.wq_of(n), res_c, num_cu=cus)
         assert planned is not None and list(fam.resident_counters()[2:] - forms_before) == [int(planned[0] == f) for f in fam.RES_FORMS], planned
         return planned[0]
@@ -357,16 +349,11 @@ def test_product_cleanup_over_the_lazy_gate_against_the_c_oracle(shape):
 
 
 def flow_counted(call):
-    """-> (result, what the product + cleanup counted: symgpu_debug_counter 36 .. 47 — None after a reseed of the row hash in this process)"""
-    def read(which):
-        v = ctypes.c_int64(0)
-        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-        return v.value
-    flows = lambda: np.array([read(pfam.FIRST_FLOW_COUNTER + k) for k in range(len(pfam.FLOW_COUNTERS))])
-    reseeds, before = read(0), flows()
+    """-> (result, what the product + cleanup counted: pfam.FLOW_COUNTERS — None after a reseed of the row hash in this process)"""
+    reseeds, before = kernels.counter('HASH_RESEEDS'), kernels.counters(pfam.FLOW_COUNTERS)
     out = call()
-    took = (flows() - before).tolist()
-    return out, (took if reseeds == 0 and read(0) == 0 else None)
+    took = (kernels.counters(pfam.FLOW_COUNTERS) - before).tolist()
+    return out, (took if reseeds == 0 and kernels.counter('HASH_RESEEDS') == 0 else None)
 
 
 @pytest.mark.parametrize('mode', ['default', 'sorted flag pass', 'full sort', 'give up', 'repeated rows', 'few rows', 'planted'])
@@ -379,7 +366,7 @@ def test_cleanup_flagged_key_flow_switches(mode, monkeypatch):
     every key has a partner; 'few rows': 3 x 2 distinct products, runs of ~10^6 equal keys; 'planted': rows that are products of two other
     rows — which plants less than the name says: 60 product rows of A * A occur twice, none of A * B; operands with planted merges of
     every multiplicity are in tests/test_gpu_pair_flows.py).
-    Every mode ran the flow it is named for (symgpu_debug_counter 36 .. 47 against the restated plan of tests/_pair_families.py): 'default'
+    Every mode ran the flow it is named for (the counters pfam.FLOW_COUNTERS against the restated plan of tests/_pair_families.py): 'default'
     and 'planted' the hash-table pass to its end, marking from bytes, the flagged keys sorted alone; 'give up' the whole array sorted behind
     a hash-table pass that did not give up; 'repeated rows' a hash-table pass that gave up on a saturated counter (45 pairs a key).  'few rows'
     does NOT reach k_find_suspects by default: the hash-table pass is launched and stops at an operand bucket of ~870 equal terms (over 255).

@@ -3,7 +3,7 @@ matrices, against the C oracle, bit for bit: reduced matrix (padding bits includ
 
 The elimination decides from the data which panel a block runs on (two-word window, four-word window, full rows in LDS), where a window
 starts and where a block ends.  The families of tests/_gf2_families.py steer those decisions (tests/test_gf2_families.py checks on the
-CPU that they have the structure they claim); symgpu_debug_counter 15 / 16 / 17 — blocks panelled by the blocked path, of these on the
+CPU that they have the structure they claim); the counters GF2_BLOCKS_PANELLED / GF2_PANEL_FULL_ROWS / GF2_PANEL_WINDOW — blocks panelled by the blocked path, of these on the
 full rows, of these on the two-word window — tell which decision was taken.  The counter tests assert FACTS a family is built for
 ("the full-row panel ran", "blocks ended early"), never exact block counts: a better heuristic passes, a lost path does not.
 
@@ -42,12 +42,7 @@ def set_schedule(monkeypatch, env):
 
 def counters():
     """(blocks panelled by the blocked path, of these on the full rows in LDS, of these on the two-word window), cumulative."""
-    v = ctypes.c_int64(0)
-    out = []
-    for which in (15, 16, 17):
-        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-        out.append(v.value)
-    return np.array(out)
+    return kernels.counters(('GF2_BLOCKS_PANELLED', 'GF2_PANEL_FULL_ROWS', 'GF2_PANEL_WINDOW'))
 
 
 _cache = {}
@@ -250,9 +245,9 @@ def test_injected_time_out_on_structured_matrices(name, R, C, monkeypatch):
 def test_injected_time_out_on_a_small_matrix_sent_through_the_blocked_path(name, R, C, monkeypatch):
     """SYMGPU_GF2_SMALL=0 sends a matrix of <= 64 rows and <= 64 words through the fused blocked schedule: plan_rref decides path and
     schedule in one place, so the matrix gets its safety copy and SYMGPU_GF2_FUSED_SELECT=2 reaches it like any other (restore, second
-    run with separate launches: counter 15 rises by twice a plain blocked run's).  Nothing is latched or reported, and the next plain
+    run with separate launches: GF2_BLOCKS_PANELLED rises by twice a plain blocked run's).  Nothing is latched or reported, and the next plain
     call takes the one-workgroup path again.  (Before the plan existed, the copy and the injection were decided from the size alone
-    and the injection was ignored here: counter 15 rose once.)"""
+    and the injection was ignored here: GF2_BLOCKS_PANELLED rose once.)"""
     p, expect = case(name, R, C)
     assert R <= 64 and p.shape[1] <= 64
     degraded = _lib.degraded()

@@ -1,14 +1,15 @@
 """GPU: every flow of the fused product + cleanup (csrc/cleanup_driver.hip plan_cleanup, cleanup_keys.hip order_flagged, pair_dups.hip) on
 operands whose answers are known BY CONSTRUCTION (tests/_pair_families.py; tests/test_pair_families.py proves them against the C oracle on
-the CPU): rows, order and coefficient bits equal the builder's answer, and the flow each call took — read from symgpu_debug_counter
-36 .. 47 — is the one the restated plan gives for the shape and the switches:
+the CPU): rows, order and coefficient bits equal the builder's answer, and the flow each call took — read from the debug counters
+FLOW_* and GIVEUP_* (kernels.counters; SYMGPU_COUNTER_LIST of include/symgpu.h says what each counts) — is the one the restated plan gives
+for the shape and the switches:
 
-  36  packed keys ordered by the complete sort               42  ... list overflow
-  37  flag pass from the operand hash tables                 43  ... operand bucket over 255 terms
-  38  flag pass behind the partial sort (k_find_suspects)    44  whole array sorted after the flag pass
-  39  a flag pass gave up                                    45  flagged keys sorted alone
-  40  hash-table pass: product bucket over 16,384 pairs      46  single terms marked from bytes (k_mark_bytes)
-  41  ... counter saturated                                  47  attempt repeated with the full 64-bit sort
+  FLOW_COMPLETE_SORT        packed keys ordered by the complete sort               GIVEUP_LIST_OVERFLOW    ... list overflow
+  FLOW_FLAGS_HASH_TABLES    flag pass from the operand hash tables                 GIVEUP_OPERAND_BUCKET   ... operand bucket over 255 terms
+  FLOW_FLAGS_PARTIAL_SORT   flag pass behind the partial sort (k_find_suspects)    FLOW_SORTED_WHOLE       whole array sorted after the flag pass
+  FLOW_FLAGS_GAVE_UP        a flag pass gave up                                    FLOW_SORTED_FLAGGED     flagged keys sorted alone
+  GIVEUP_PRODUCT_BUCKET     hash-table pass: product bucket over 16,384 pairs      FLOW_MARKED_FROM_BYTES  single terms marked from bytes (k_mark_bytes)
+  GIVEUP_COUNTER_SATURATED  ... counter saturated                                  FLOW_FULL_SORT_REPEAT   attempt repeated with the full 64-bit sort
 
 The families put pairs that share a row where the flag passes branch — the corners of the pair index, both groups of the 8,192-bucket
 form, product bucket 0 of P * P, rows shared between the operands (the zero-word rule), 4-bit counters at and past saturation — and heavy
@@ -18,13 +19,11 @@ spurious row here, or a wrong Gaussian integer.  Sums are exact in any order: th
 What does not depend on the hash seed is asserted as a path: up to 8 pairs on one key never saturate a 4-bit counter (the pass completes,
 the flagged keys are sorted alone, marking from bytes), 16 and more always do; every row twice always overflows the list; the blocks
 always burst a product or an operand bucket.  15 pairs on one key: the result only — one chance hit on the same counter tips it.  After a
-reseed in this process (counter 0) only the result is asserted."""
-import ctypes
-
+reseed in this process (HASH_RESEEDS) only the result is asserted."""
 import numpy as np
 import pytest
 
-from symmer_amd import kernels, _lib
+from symmer_amd import kernels
 import _pair_families as fam
 
 pytestmark = pytest.mark.gpu
@@ -50,31 +49,21 @@ def set_switches(monkeypatch, env):
         monkeypatch.setenv(k, v)                                      # read per call (cleanup_driver.hip read_cleanup_switches, pair_dups_fits)
 
 
-def counter(which):
-    v = ctypes.c_int64(0)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
-
-
-def flow_counters():
-    return np.array([counter(fam.FIRST_FLOW_COUNTER + k) for k in range(len(fam.FLOW_COUNTERS))])
-
-
 def describe(delta):
     return '[' + '; '.join(f'{fam.FLOW_COUNTERS[k]}' + (f' x {d}' if d != 1 else '') for k, d in enumerate(delta) if d) + ']'
 
 
 def counted(call, what):
     """-> (result of the call, what it counted — None after a reseed of the row hash, in this call or earlier in the process)."""
-    reseeds, before = counter(0), flow_counters()
+    reseeds, before = kernels.counter('HASH_RESEEDS'), kernels.counters(fam.FLOW_COUNTERS)
     out = call()
-    delta = (flow_counters() - before).tolist()
+    delta = (kernels.counters(fam.FLOW_COUNTERS) - before).tolist()
     print(f'{what}: {describe(delta)}')
-    return out, (delta if reseeds == 0 and counter(0) == 0 else None)
+    return out, (delta if reseeds == 0 and kernels.counter('HASH_RESEEDS') == 0 else None)
 
 
 def assert_flow(delta, want, what):
-    """One attempt with the counters `want`.  (Counter 47 is left open: a run of more than 48 equal sorted key prefixes that holds a second key
+    """One attempt with the counters `want`.  (FLOW_FULL_SORT_REPEAT is left open: a run of more than 48 equal sorted key prefixes that holds a second key
     — the identity segment of P * P beside one chance neighbour — sends the call through a second attempt with the full 64-bit sort, which counts
     nothing else.  It depends on the hash seed and is not a flow of the plan.)"""
     if delta is not None:
@@ -214,7 +203,7 @@ def test_blocks_burst_the_buckets(monkeypatch):
     counter as well); block(300, 5): 300 terms in one operand bucket (over 255: the pass stops before it looks at a pair); block(300, 300)
     behind the partial sort: a run of 90,000 equal keys, past the 64 steps of 1,024 keys that k_find_suspects reads on — it gives up and
     the whole array is sorted.  (A run of more than 48 equal 32-bit prefixes that holds a second key repeats the attempt with the full sort:
-    counter 47 may or may not move here.)"""
+    FLOW_FULL_SORT_REPEAT may or may not move here.)"""
     G, B, S, L, O, W, A = fam.C_GIVEUP, fam.C_R_BUCKET, fam.C_R_SAT, fam.C_R_LIST, fam.C_R_OPERAND, fam.C_WHOLE, fam.C_ALONE
     shape = (1255, 1254)
 

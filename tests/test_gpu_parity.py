@@ -1221,7 +1221,7 @@ def test_jordan_and_reindex_golden(case):
 def test_rotate_golden_rows_left_in_memory(case, monkeypatch):
     """SYMGPU_ROT_HBM=2 makes the one-launch rotation kernel leave the rows in memory (the form operators beyond the chip's LDS take,
     csrc/rotate_resident_kernel.hip) whatever the operator's size: the reference-generated cases, every row length among them.  Every one-launch
-    rotation of the case (completed or failed) was launched in that form and in no other: symgpu_debug_counter 35 against 1 + 2, 33 and 34."""
+    rotation of the case (completed or failed) was launched in that form and in no other: the counter RESIDENT_ROWS_IN_MEMORY against RESIDENT_DONE + RESIDENT_FAILED, RESIDENT_LDS and RESIDENT_REGISTERS."""
     import _rotation_families as fam
     monkeypatch.setenv('SYMGPU_ROT_HBM', '2')
     before = fam.resident_counters()

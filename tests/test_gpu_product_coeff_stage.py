@@ -4,8 +4,7 @@ outer row per workgroup.  The shapes below end packed bytes and 256-term pieces 
 outer rows than one launch's grid.y holds, and write a slab with o_begin > 0 into an output handle that already holds another slab.
 The slab and grid.y cases also run with the switches that select the other paths of the product (word-major or wide coefficient kernel
 followed by the plain row stream, rows only): each path has its own o_begin and batch-offset arithmetic; which path served a call is read from
-symgpu_debug_counter 48 .. 52 (one per ProductPath, bumped at the switch of symgpu_mul_allpairs_dev)."""
-import ctypes
+the counters PRODUCT_* (one per ProductPath, bumped at the switch of symgpu_mul_allpairs_dev)."""
 
 import numpy as np
 import pytest
@@ -28,16 +27,12 @@ def gaussian(rng, t):
 
 
 PATHS = ('rows only', 'phase stream', 'wide coefficients, then rows', 'word-major coefficients, then rows', 'word-major coefficients beside rows')
+PATH_COUNTERS = ('PRODUCT_ROWS_ONLY', 'PRODUCT_PHASE_STREAM', 'PRODUCT_WIDE_COEFF_THEN_ROWS', 'PRODUCT_WORD_MAJOR_THEN_ROWS', 'PRODUCT_WORD_MAJOR_BESIDE_ROWS')
 ROWS_ONLY, PHASE_STREAM, WIDE, WORD_MAJOR = 0, 1, 2, 3
 
 
 def path_counters():
-    v = ctypes.c_int64(0)
-    out = []
-    for which in range(48, 53):
-        _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-        out.append(v.value)
-    return np.array(out)
+    return kernels.counters(PATH_COUNTERS)
 
 
 def counted(call, path, what, calls=1):

@@ -1,7 +1,7 @@
 """Device residency behind the drop-in classes ("device-resident operands ... so multi-step callers avoid PCIe").
 
 Results of the kernels stay on the GPU (`PauliwordOp._dev`) and reach the host when `symp_matrix` / `packed` / `coeff_vec` are read;
-operands are uploaded once.  The library counts the payload bytes it copies in either direction (`symgpu_debug_counter` 7-10), and
+operands are uploaded once.  The library counts the payload bytes it copies in either direction (the counters H2D_BYTES, D2H_BYTES, OP_UPLOADS, OP_DOWNLOADS), and
 these tests assert through those counters that the reference's multi-step callers — `(P * P) * Q`, and rotate -> project -> cleanup
 of `symmer/projection/base.py:44-124` — move their operator once in and once out, with results identical to the oracle's."""
 import numpy as np

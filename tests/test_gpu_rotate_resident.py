@@ -1,13 +1,12 @@
 """The one-launch, LDS-resident rotation kernel (symmer_amd/csrc/rotate_resident_kernel.hip, planned and launched from rotate_resident.hip) against the multi-launch paths (bit for bit:
 rows, row order, coefficients) and against the NumPy oracle of PauliwordOp._rotate_by_single_Pword (reference base.py:1090-1161).
 The kernel only takes operators whose duplicate status and row hashes are known, i.e. from the second rotation of a handle on."""
-import ctypes
 import os
 import subprocess
 import sys
 import numpy as np
 import pytest
-from symmer_amd import _lib, kernels, packing
+from symmer_amd import kernels, packing
 from symmer_amd.kernels import DeviceOp
 from oracle import oracle_np as onp
 from _golden import assert_op_equal
@@ -16,12 +15,6 @@ import _rotation_families as fam
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def counter(which):
-    v = ctypes.c_int64(-1)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
 
 
 def dyadic(rng, t):
@@ -47,9 +40,9 @@ def run_both(op, q_packed, ang, monkeypatch):
     monkeypatch.setenv('SYMGPU_ROT_RESIDENT', '0')
     a, allc_a = kernels.rotate_single_dev(op, q_packed, ang)
     monkeypatch.delenv('SYMGPU_ROT_RESIDENT')
-    before = counter(1)
+    before = kernels.counter('RESIDENT_DONE')
     b, allc_b = kernels.rotate_single_dev(op, q_packed, ang)
-    assert counter(1) == before + 1, 'the resident kernel did not take (or did not complete) the rotation'
+    assert kernels.counter('RESIDENT_DONE') == before + 1, 'the resident kernel did not take (or did not complete) the rotation'
     assert allc_a == allc_b
     ra = None if allc_a else a.download()
     rb = None if allc_b else b.download()
@@ -73,10 +66,10 @@ def test_resident_rotation_equals_multilaunch_and_oracle(n, T, monkeypatch):
     up.free()
     r0, c0 = op.download()
     assert np.array_equal(r0, packing.pack_rows(symp)) and np.array_equal(c0, c)
-    # which residency form the launches take (symgpu_debug_counter 33 / 34 / 35): the plan, restated for this device — rows in LDS at these sizes
+    # which residency form the launches take (fam.RES_FORM_COUNTERS): the plan, restated for this device — rows in LDS at these sizes
     planned = fam.plan_resident(symp.shape[0], fam.wq_of(n), fam.resident_constants(fam.resident_header_text()), num_cu=fam.device_cu_count())
     assert planned is not None and planned[0] == 'Lds', planned
-    forms_before = [counter(33 + i) for i in range(3)]
+    forms_before = kernels.counters(fam.RES_FORM_COUNTERS)
     for ang in ANGLES:
         ra, rb = run_both(op, qp, ang, monkeypatch)
         er, ec = onp.rotate_by_single_pword(symp, c, q, ang)
@@ -92,7 +85,7 @@ def test_resident_rotation_equals_multilaunch_and_oracle(n, T, monkeypatch):
         else:
             keep_d, keep_o = np.abs(rb[1]) > TOL, np.abs(ec) > TOL
             assert np.array_equal(rb[0][keep_d], got[keep_o]) and np.allclose(rb[1][keep_d], ec[keep_o], rtol=0, atol=TOL)
-    launched = [counter(33 + i) - forms_before[i] for i in range(3)]
+    launched = (kernels.counters(fam.RES_FORM_COUNTERS) - forms_before).tolist()
     assert launched == [len(ANGLES) if f == planned[0] else 0 for f in fam.RES_FORMS], (launched, planned)   # one launch per resident call
     op.free()
 
@@ -123,13 +116,13 @@ def test_resident_chain_of_rotations_vs_oracle():
     angs = [0.3, np.pi / 2, -0.9, 0.3, 3 * np.pi / 2, 1.7]
     cur = DeviceOp.upload(packing.pack_rows(symp), c)
     es, ec = symp, c
-    before = counter(1)
+    before = kernels.counter('RESIDENT_DONE')
     for q, ang in zip(qs + [q0], angs + [0.3]):
         res, allc = kernels.rotate_single_dev(cur, packing.pack_rows(q.reshape(1, -1))[0], ang)
         es, ec = onp.rotate_by_single_pword(es, ec, q, ang)
         if not allc:
             cur.free(); cur = res
-    assert counter(1) >= before + 5
+    assert kernels.counter('RESIDENT_DONE') >= before + 5
     rows, coeff = cur.download()
     cur.free()
     got = packing.pack_rows(es)
@@ -200,7 +193,7 @@ def chain_forms_of(n, T):
 def test_every_chain_form_gives_the_same_run_in_one_process(n, T, K, monkeypatch):
     """The path-selection switches are read on every call: the LDS-resident single-workgroup kernel, the L2-resident
     one, the two-launch and the four-launch forms and the register chain must all return the same rows, order and coefficients.
-    Which form served a call is read from symgpu_debug_counter 22 .. 26; the cases together reach all five (rows of 130 qubits are 3
+    Which form served a call is read from the counters fam.FORM_COUNTERS; the cases together reach all five (rows of 130 qubits are 3
     chunks wide: no power of two, so they take the four-launch form where the others take the register chain or the two-launch form)."""
     assert {f for case in CHAIN_FORM_CASES for f in chain_forms_of(*case[:2])} == set(range(5))
     rng = np.random.default_rng(31000 + n + T)
@@ -214,10 +207,10 @@ def test_every_chain_form_gives_the_same_run_in_one_process(n, T, K, monkeypatch
     for env, form in zip(CHAIN_SETTINGS, chain_forms_of(n, T)):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        before = [counter(22 + i) for i in range(5)]
+        before = kernels.counters(fam.FORM_COUNTERS)
         out = kernels.rotate_clifford_chain_dev(dev, qs, ks)
-        served = [counter(22 + i) - before[i] for i in range(5)]
-        assert served == [int(i == form) for i in range(5)], f'{env}: expected one call by {fam.FORMS[form]}, counters 22 .. 26 rose by {served}'
+        served = (kernels.counters(fam.FORM_COUNTERS) - before).tolist()
+        assert served == [int(i == form) for i in range(5)], f'{env}: expected one call by {fam.FORMS[form]}, the counters {fam.FORM_COUNTERS} rose by {served}'
         results.append(out.download())
         out.free()
         for k in env:
@@ -229,7 +222,7 @@ def test_every_chain_form_gives_the_same_run_in_one_process(n, T, K, monkeypatch
 
 def test_growing_rotation_chain_does_not_meet_hipmalloc():
     """VERDICT r2 (API edge): a chain of non-Clifford rotations whose term count grows meets a new result size with every step; the
-    allocator's arena serves those sizes without a hipMalloc per step (debug counter 3), so the first pass costs what later ones cost."""
+    allocator's arena serves those sizes without a hipMalloc per step (counter DEV_MALLOC_CALLS), so the first pass costs what later ones cost."""
     rng = np.random.default_rng(3)
     n = 1000
     P = DeviceOp.random(20000, n, 0.3, seed=77)
@@ -245,11 +238,11 @@ def test_growing_rotation_chain_does_not_meet_hipmalloc():
             sizes.append(cur.n_terms)
         cur.free()
         return sizes
-    m0 = counter(3)
+    m0 = kernels.counter('DEV_MALLOC_CALLS')
     sizes = chain()
-    m1 = counter(3)
+    m1 = kernels.counter('DEV_MALLOC_CALLS')
     assert sizes == sorted(sizes) and sizes[-1] > 5 * sizes[0] // 2
     assert m1 - m0 <= 3, f'{m1 - m0} device allocations went to hipMalloc during the first pass of a 5-step chain'
     chain()
-    assert counter(3) == m1
+    assert kernels.counter('DEV_MALLOC_CALLS') == m1
     P.free()

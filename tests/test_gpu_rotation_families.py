@@ -3,16 +3,15 @@ rotate_driver.hip plan_chain) and every stage that completes a single rotation, 
 popcount formula (tests/_rotation_families.py; tests/test_rotation_families.py proves them against the NumPy oracle on the CPU).  Every
 case is compared bit for bit — rows, row order, coefficients — with the table-based expectation or, above 400,000 Pauli codes, with the
 packed step (proven against the table on the CPU); no case goes without, whatever its size.  The form that served each call is asserted
-through symgpu_debug_counter:
+through the debug counters (kernels.counters; SYMGPU_COUNTER_LIST of include/symgpu.h says what each counts):
 
-  22 register chain   23 LDS-resident   24 single workgroup   25 two launches per rotation   26 four launches per rotation
-  27 / 28  segments of the register chain sorted by the one-launch / the multi-launch sort
-  29 / 30 / 31  single rotations completed by the hash join / the Clifford fast path / the general path; 32: of 31, after the duplicate check
+  CHAIN_REGISTERS   CHAIN_LDS   CHAIN_SINGLE_WORKGROUP   CHAIN_TWO_LAUNCHES (per rotation)   CHAIN_FOUR_LAUNCHES (per rotation)
+  CHAIN_SORT_ONE_LAUNCH / CHAIN_SORT_LAUNCHES  segments of the register chain sorted by the one-launch / the multi-launch sort
+  ROTATE_HASH_JOIN / ROTATE_CLIFFORD_FAST / ROTATE_GENERAL  single rotations by the stage that completed them;
+  ROTATE_GENERAL_BY_DUP_CHECK: of ROTATE_GENERAL, after the duplicate check
 
 Only the switches of the library as shipped are used (SYMGPU_CHAIN_REG, SYMGPU_CHAIN_LOCAL_T); everything else is chosen by shape.
 (One qubit cannot hold 129 distinct rows, so the Wq = 1 row length that is no multiple of 64 is n = 40 and not 64 Wq - 63 = 1.)"""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -23,9 +22,9 @@ import _rotation_families as fam
 
 pytestmark = pytest.mark.gpu
 
-REGISTERS, LDS, SINGLE, TWO_LAUNCH, FOUR_LAUNCH = range(5)              # counters 22 .. 26
-SORT_ONE, SORT_MULTI = 5, 6                                             # 27, 28
-JOIN, FAST, GENERAL, DUP_GENERAL = 7, 8, 9, 10                          # 29 .. 32
+COUNTERS = fam.FORM_COUNTERS + ('CHAIN_SORT_ONE_LAUNCH', 'CHAIN_SORT_LAUNCHES', 'ROTATE_HASH_JOIN', 'ROTATE_CLIFFORD_FAST', 'ROTATE_GENERAL',
+                                'ROTATE_GENERAL_BY_DUP_CHECK')
+REGISTERS, LDS, SINGLE, TWO_LAUNCH, FOUR_LAUNCH, SORT_ONE, SORT_MULTI, JOIN, FAST, GENERAL, DUP_GENERAL = range(11)   # index COUNTERS
 NAMES = fam.FORMS + ('one-launch sort', 'multi-launch sort', 'hash join', 'Clifford fast path', 'general path', 'duplicate check -> general path')
 ENV_NAMES = ('SYMGPU_CHAIN_REG', 'SYMGPU_CHAIN_LOCAL_T', 'SYMGPU_ROT_RESIDENT', 'SYMGPU_ROTATE_GENERAL', 'SYMGPU_ROT_HBM')
 DEFAULT = {}
@@ -41,14 +40,8 @@ def _seen(request):
     SEEN.add(request.function.__name__)
 
 
-def counter(which):
-    v = ctypes.c_int64(-1)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
-
-
 def counters():
-    return np.array([counter(w) for w in range(22, 33)], dtype=np.int64)
+    return kernels.counters(COUNTERS)
 
 
 def set_switches(monkeypatch, env):
@@ -322,9 +315,9 @@ def test_perform_rotations_counts_two_runs_around_a_single_rotation(resident, mo
     set_switches(monkeypatch, {} if resident is None else {'SYMGPU_ROT_RESIDENT': resident})
     P = PauliwordOp(symp, case.coeff)
     rotations = [(PauliwordOp(qsymp[r].reshape(1, -1), [1]), angles[r]) for r in range(7)]
-    before, resident_before = counters(), counter(1)
+    before, resident_before = counters(), kernels.counter('RESIDENT_DONE')
     R = P.perform_rotations(rotations)
-    delta, by_resident = counters() - before, counter(1) - resident_before
+    delta, by_resident = counters() - before, kernels.counter('RESIDENT_DONE') - resident_before
     global TALLY
     TALLY += delta
     took = [NAMES[i] for i in range(11) for _ in range(int(delta[i]))] + ['one-launch rotation'] * by_resident
@@ -339,12 +332,12 @@ def test_perform_rotations_counts_two_runs_around_a_single_rotation(resident, mo
 
 # ---------------------------------------------------------------- 6. the stages of a single rotation ----------------------------------------
 def single(dev, q, angle):
-    before, resident_before = counters(), counter(1)
+    before, resident_before = counters(), kernels.counter('RESIDENT_DONE')
     res, allc = kernels.rotate_single_dev(dev, q, angle)
     delta = counters() - before
     global TALLY
     TALLY += delta
-    assert counter(1) == resident_before and not delta[:7].any(), 'not a multi-launch single rotation'
+    assert kernels.counter('RESIDENT_DONE') == resident_before and not delta[:7].any(), 'not a multi-launch single rotation'
     assert not allc
     try:
         return res.download(), delta[JOIN:].tolist()

@@ -3,9 +3,9 @@ inside the library at the same time; every call holds its device's context lock 
 Each worker runs every hot path on operators of its own, in its own shuffled order, and checks every result against the C oracle or the
 NumPy restatement, exactly as the single-thread tests of the same path do.  All expected results are computed on the main thread before
 any worker starts.  Every task has a shape of its own, and the shapes differ by worker, so two calls never read back equal counts by
-accident.  The library records where a call USES a context's state, whichever lock the call took: symgpu_debug_counter 12 (most threads
-seen using one context at once) must stay 1 and 14 (uses of a context by a call that does not hold its lock) must stay 0, and 13 (calls
-that waited for a busy context) must grow, which shows that the calls did overlap."""
+accident.  The library records where a call USES a context's state, whichever lock the call took: the counter CTX_MAX_THREADS (most
+threads seen using one context at once) must stay 1 and CTX_UNLOCKED_USES (uses of a context by a call that does not hold its lock) must
+stay 0, and CTX_WAITS (calls that waited for a busy context) must grow, which shows that the calls did overlap."""
 import ctypes
 import threading
 
@@ -29,15 +29,9 @@ def dyadic(rng, t):
     return (rng.integers(-8, 9, t) + 1j * rng.integers(-8, 9, t)) / 16.0
 
 
-def debug_counter(which):
-    v = ctypes.c_int64(0)
-    _lib.check(_lib.lib().symgpu_debug_counter(which, ctypes.addressof(v)))
-    return v.value
-
-
 def assert_serialised():
-    assert debug_counter(14) == 0, f'{debug_counter(14)} uses of a context by calls that did not hold its lock'
-    assert debug_counter(12) == 1, f'{debug_counter(12)} threads used one context at once'
+    assert kernels.counter('CTX_UNLOCKED_USES') == 0, f'{kernels.counter("CTX_UNLOCKED_USES")} uses of a context by calls that did not hold its lock'
+    assert kernels.counter('CTX_MAX_THREADS') == 1, f'{kernels.counter("CTX_MAX_THREADS")} threads used one context at once'
 
 
 def run_workers(works, timeout=JOIN_TIMEOUT_S):
@@ -238,7 +232,7 @@ def test_threads_share_one_device(n_workers):
     for w in range(n_workers):                               # expected results first, on this thread only
         rng = np.random.default_rng(9000 + 100 * n_workers + w)
         checks.append({name: make(rng, w) for name, make in TASKS.items()})
-    waited, resident = debug_counter(13), debug_counter(1)
+    waited, resident = kernels.counter('CTX_WAITS'), kernels.counter('RESIDENT_DONE')
 
     def work(w):
         order = np.random.default_rng(w)
@@ -252,11 +246,11 @@ def test_threads_share_one_device(n_workers):
                         raise AssertionError(f'worker {w}, iteration {it}, task {name}: {e}') from e
         return go
     run_workers([work(w) for w in range(n_workers)])
-    print(f'{n_workers} workers: counter 12 = {debug_counter(12)}, counter 14 = {debug_counter(14)}, '
-          f'counter 13 grew by {debug_counter(13) - waited}, one-launch rotations: {debug_counter(1) - resident}')
+    print(f'{n_workers} workers: CTX_MAX_THREADS = {kernels.counter("CTX_MAX_THREADS")}, CTX_UNLOCKED_USES = {kernels.counter("CTX_UNLOCKED_USES")}, '
+          f'CTX_WAITS grew by {kernels.counter("CTX_WAITS") - waited}, one-launch rotations: {kernels.counter("RESIDENT_DONE") - resident}')
     assert_serialised()
-    assert debug_counter(13) > waited, 'no call ever waited for another: the workers did not overlap'
-    assert debug_counter(1) > resident, 'the one-launch rotation never ran'
+    assert kernels.counter('CTX_WAITS') > waited, 'no call ever waited for another: the workers did not overlap'
+    assert kernels.counter('RESIDENT_DONE') > resident, 'the one-launch rotation never ran'
 
 
 def test_shared_read_only_operand():
@@ -306,7 +300,7 @@ def test_shared_read_only_operand():
 def test_threads_on_handles_of_another_device():
     """Threads whose current device is 0 work on handles of device 1 while other threads work on device 1 directly: a call runs on, and
     locks, its handles' device.  A guard that locked the thread's device instead would leave the device-0 threads using device 1's
-    context without its lock: counter 14 would count every such call, and counter 12 would see two threads on device 1 at once."""
+    context without its lock: CTX_UNLOCKED_USES would count every such call, and CTX_MAX_THREADS would see two threads on device 1 at once."""
     if _lib.device_count() < 2:
         pytest.skip('needs two devices')
     rc = _lib.load().symgpu_init_all(2)
@@ -319,7 +313,7 @@ def test_threads_on_handles_of_another_device():
         base = packing.pack_rows(rng.random((T // 2, 2 * n)) < 0.3)
         rows, coeff = base[rng.integers(0, base.shape[0], T)], dyadic(rng, T)
         plans.append((rows, coeff, oc.cleanup(rows, coeff, 1e-15)))
-    waited = debug_counter(13)
+    waited = kernels.counter('CTX_WAITS')
 
     def work(w):
         rows, coeff, (er, ec) = plans[w]
@@ -344,4 +338,4 @@ def test_threads_on_handles_of_another_device():
     finally:
         _lib.set_device(0)
     assert_serialised()
-    assert debug_counter(13) > waited
+    assert kernels.counter('CTX_WAITS') > waited

@@ -350,6 +350,44 @@ def test_rotation_args_clifford_detection(angle):
         assert k == -1 and cos_t == np.cos(angle) and sin_t == np.sin(angle)
 
 
+# ---- the debug counters: one table (SYMGPU_COUNTER_LIST, include/symgpu.h), ids frozen ----------------------------------------------
+# The freeze: the ids are part of the C ABI (outside binders pass the numbers).  A name may only ever be ADDED here, at the end.
+COUNTER_IDS = [
+    (0, 'HASH_RESEEDS'), (1, 'RESIDENT_DONE'), (2, 'RESIDENT_FAILED'), (3, 'DEV_MALLOC_CALLS'), (4, 'RESIDENT_NS_PREPARE'),
+    (5, 'RESIDENT_NS_LAUNCH'), (6, 'RESIDENT_NS_WAIT'), (7, 'H2D_BYTES'), (8, 'D2H_BYTES'), (9, 'OP_UPLOADS'), (10, 'OP_DOWNLOADS'),
+    (11, 'CANARY_HITS'), (12, 'CTX_MAX_THREADS'), (13, 'CTX_WAITS'), (14, 'CTX_UNLOCKED_USES'), (15, 'GF2_BLOCKS_PANELLED'),
+    (16, 'GF2_PANEL_FULL_ROWS'), (17, 'GF2_PANEL_WINDOW'), (18, 'COMMUTE_REGISTER_TILE'), (19, 'COMMUTE_WIDE_ROWS'), (20, 'COMMUTE_M4R_TILE'),
+    (21, 'COMMUTE_M4R_STREAMK'), (22, 'CHAIN_REGISTERS'), (23, 'CHAIN_LDS'), (24, 'CHAIN_SINGLE_WORKGROUP'), (25, 'CHAIN_TWO_LAUNCHES'),
+    (26, 'CHAIN_FOUR_LAUNCHES'), (27, 'CHAIN_SORT_ONE_LAUNCH'), (28, 'CHAIN_SORT_LAUNCHES'), (29, 'ROTATE_HASH_JOIN'),
+    (30, 'ROTATE_CLIFFORD_FAST'), (31, 'ROTATE_GENERAL'), (32, 'ROTATE_GENERAL_BY_DUP_CHECK'), (33, 'RESIDENT_LDS'), (34, 'RESIDENT_REGISTERS'),
+    (35, 'RESIDENT_ROWS_IN_MEMORY'), (36, 'FLOW_COMPLETE_SORT'), (37, 'FLOW_FLAGS_HASH_TABLES'), (38, 'FLOW_FLAGS_PARTIAL_SORT'),
+    (39, 'FLOW_FLAGS_GAVE_UP'), (40, 'GIVEUP_PRODUCT_BUCKET'), (41, 'GIVEUP_COUNTER_SATURATED'), (42, 'GIVEUP_LIST_OVERFLOW'),
+    (43, 'GIVEUP_OPERAND_BUCKET'), (44, 'FLOW_SORTED_WHOLE'), (45, 'FLOW_SORTED_FLAGGED'), (46, 'FLOW_MARKED_FROM_BYTES'),
+    (47, 'FLOW_FULL_SORT_REPEAT'), (48, 'PRODUCT_ROWS_ONLY'), (49, 'PRODUCT_PHASE_STREAM'), (50, 'PRODUCT_WIDE_COEFF_THEN_ROWS'),
+    (51, 'PRODUCT_WORD_MAJOR_THEN_ROWS'), (52, 'PRODUCT_WORD_MAJOR_BESIDE_ROWS'), (53, 'CSR_FILL_LDS'), (54, 'CSR_FILL_SCRATCH'),
+]
+
+
+def test_debug_counter_ids_and_names_are_frozen():
+    """symgpu_debug_counter_name spells exactly the table above (so does the map the Python side builds from it), NULL outside it; every id
+    reads without a device and 55 is the first that does not; an unknown name is a KeyError that names it."""
+    from symmer_amd import kernels
+    lib = _lib.load()
+    assert [i for i, _ in COUNTER_IDS] == list(range(55)) and len({name for _, name in COUNTER_IDS}) == 55
+    got = [(i, lib.symgpu_debug_counter_name(i)) for i in range(55)]
+    assert [(i, name.decode('ascii') if name is not None else None) for i, name in got] == COUNTER_IDS
+    assert lib.symgpu_debug_counter_name(-1) is None and lib.symgpu_debug_counter_name(55) is None
+    assert _lib.counter_ids() == {name: i for i, name in COUNTER_IDS}
+    v = ctypes.c_int64(-1)
+    for i, name in COUNTER_IDS:
+        assert lib.symgpu_debug_counter(i, ctypes.addressof(v)) == _lib.OK and v.value >= 0, name
+        assert kernels.counter(name) == v.value
+    assert lib.symgpu_debug_counter(55, ctypes.addressof(v)) == _lib.E_INVALID and lib.symgpu_debug_counter(-1, ctypes.addressof(v)) == _lib.E_INVALID
+    assert kernels.counters(['H2D_BYTES', 'CSR_FILL_SCRATCH']).dtype == np.int64
+    with pytest.raises(KeyError, match='no_such'):
+        kernels.counter('no_such')
+
+
 # ---- every exported entry point that touches a device context holds that context's lock (SG_ENTER, common.h) ------------------------
 # The calls that deliberately take no lock, each with its reason.  Every name here must still be defined (the list cannot rot).
 UNLOCKED_ENTRY_POINTS = {
@@ -370,7 +408,9 @@ UNLOCKED_ENTRY_POINTS = {
     'symgpu_device_count': 'asks the runtime; touches no context',
     'symgpu_n_initialised': 'counts ready contexts; touches none of their state',
     'symgpu_degraded': 'has its own mutex',
+    'symgpu_last_error': "returns the calling thread's own error text",
     'symgpu_debug_counter': 'reads atomic counters',
+    'symgpu_debug_counter_name': 'returns a string literal of the counter table; touches no context',
     'symgpu_op_info': "reads the handle's own fields (a handle has one owner)",
     'symgpu_dev_free': "allocator only: files the block under its owning device, under the allocator's mutex; needs no context",
 }
@@ -400,10 +440,11 @@ def _strip_c_comments_and_strings(src):
 
 
 def _entry_point_bodies(src):
-    """{name: body} of every `int symgpu_*(...) {...}` definition in one translation unit (declarations are skipped)."""
+    """{name: body} of every `int symgpu_*(...) {...}` / `const char *symgpu_*(...) {...}` definition in one translation unit
+    (declarations are skipped)."""
     clean = _strip_c_comments_and_strings(src)
     bodies = {}
-    for m in re.finditer(r'^int\s+(symgpu_\w+)\s*\(', clean, re.M):
+    for m in re.finditer(r'^(?:int\s+|const char \*)(symgpu_\w+)\s*\(', clean, re.M):
         depth, i = 0, m.end() - 1
         while True:                                    # the parameter list
             depth += {'(': 1, ')': -1}.get(clean[i], 0)
@@ -451,9 +492,9 @@ def test_every_entry_point_takes_its_context_lock():
     assert not problems, '\n'.join(problems)
     assert len(bodies) >= 80, f'the scan found only {len(bodies)} entry points: has the definition style changed?'
     assert all(reason.strip() for reason in UNLOCKED_ENTRY_POINTS.values())
-    # every entry point the header declares is defined where the scan looks (an `int` definition), except the one that returns text
+    # every entry point the header declares is defined where the scan looks
     header = open(os.path.join(ROOT, 'include', 'symgpu.h')).read()
-    declared = set(re.findall(r'^int\s+(symgpu_\w+)\s*\(', _strip_c_comments_and_strings(header), re.M))
+    declared = set(re.findall(r'^(?:int\s+|const char \*)(symgpu_\w+)\s*\(', _strip_c_comments_and_strings(header), re.M))
     assert declared <= set(bodies), f'declared but not found by the scan: {sorted(declared - set(bodies))}'
 
 
