@@ -471,6 +471,31 @@ int symgpu_relation_degrees_dev(symgpu_op_t op, int relation, int64_t *deg_host 
 int symgpu_clique_colour_dev(symgpu_op_t op, int relation, const int64_t *order_host /* [T], a permutation */,
                              int32_t *colour_host /* [T], by term index */, int64_t *n_colours, int64_t *info /* [4] or NULL */);
 
+/* ---- h: noncontextual operators (noncontextual_op.py:502-531 noncontextual_reconstruction, :533-554 get_energy, :686-704
+ * energy_via_brute_force; csrc/noncon.hip) ------------------------------------------------------------------------------------------
+ * symgpu_noncon_signs_dev   signs[k] for every term k of `terms`: the generators of `gens` that row k of `sel` selects (bit j % 64 of word
+ *   sel[k * sel_words + j / 64] selects generator j; bits at or above the generator count are not read) are multiplied in generator order,
+ *   starting from the identity, under the phase rule of symgpu_mul_allpairs.  +1 or -1 if the product is + or - the term's own Pauli
+ *   string; 0 if its row differs from the term's or its phase is +-i.  sel and signs are host arrays; coefficients are not read.
+ * symgpu_noncon_search   the minimum over all 2^n_free assignments m of
+ *       E(m) = sum_{clique[k] = -1} coeff[k] s_k(m) - sqrt( sum_{i < n_cliques} ( sum_{clique[k] = i} coeff[k] s_k(m) )^2 ),
+ *       s_k(m) = (-1)^popcount(mask[k] & m),
+ *   as Walsh-Hadamard transforms blocked in LDS: O(n_free 2^n_free) work, nothing but the T terms read from memory.  Bit b of m set means
+ *   that free generator number n_free-1-b (in generator order) is assigned -1; mask[k] has bit b set iff term k's reconstruction uses that
+ *   generator.  coeff, mask, clique: host arrays [T]; clique[k] = -1 for a term outside the cliques, else 0 .. n_cliques-1.
+ *   *best_energy, *best_mask: the minimum and its assignment; among assignments whose computed energies compare equal the LARGEST m wins
+ *   (the reference's `min` over itertools.product([-1, 1], ...) keeps the first minimum and -1 sorts first) — for T = 0 every energy is 0.
+ *   energies (may be NULL; ignored for n_free > 24): double [2^n_free], E(m) at index m.  Two calls with equal input return identical
+ *   bytes: every sum is taken in an order that depends on the input alone (no floating-point atomics).
+ *   SYMGPU_E_INVALID: n_free outside 0 .. 40 (a refusal bound, not a performance claim), n_cliques < 0, T < 0, a clique number outside
+ *   -1 .. n_cliques-1, a mask bit at or above n_free, a coefficient that is not finite, coefficients whose magnitudes sum beyond 1e154 (below that no
+ *   sum or square overflows: every energy is a finite number), a null best_energy or best_mask.
+ *   info (may be NULL) int64 [4]: [0] L, the assignment bits a workgroup holds in LDS (three double[2^L] vectors); [1] the blocks of 2^min(n_free, L)
+ *   assignments, 2^(n_free - min(n_free, L)); [2] the entries folded per block (T); [3] the workgroups launched. */
+int symgpu_noncon_signs_dev(symgpu_op_t terms, symgpu_op_t gens, const uint64_t *sel /* [T][sel_words] */, int sel_words, int8_t *signs /* [T] */);
+int symgpu_noncon_search(const double *coeff, const uint64_t *mask, const int32_t *clique, int64_t T, int n_free, int64_t n_cliques,
+                         double *best_energy, uint64_t *best_mask, double *energies /* [2^n_free] or NULL */, int64_t *info /* [4] or NULL */);
+
 /* ---- e: multi-GPU (one process per GPU; RCCL over xGMI) ------------------------------------------- */
 #define SYMGPU_UNIQUE_ID_BYTES 128
 int symgpu_comm_available(void);                                                /* librccl loadable? (no device, no collective) */

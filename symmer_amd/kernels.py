@@ -296,6 +296,49 @@ def clique_colouring_dev(op, relation, order, want_info=False):
     return (colours, n_colours.value, info) if want_info else (colours, n_colours.value)
 
 
+# ---- noncontextual operators (csrc/noncon.hip) ---------------------------------------------------------------------------------------
+NONCON_MAX_FREE = 40                         # symgpu_noncon_search refuses more free generators
+
+
+def noncon_signs_dev(terms, gens, selection):
+    """int8[T]: for every term of the device operator ``terms`` the sign of the product, in generator order, of the terms of ``gens`` that
+    row k of ``selection`` (bool[T, g]) selects: +1 / -1 if the product is +/- the term, 0 if it is another Pauli string or carries a phase
+    +-i (``symgpu_noncon_signs_dev``)."""
+    selection = np.asarray(selection).astype(bool)
+    t, g = terms.n_terms, gens.n_terms
+    assert selection.shape == (t, g), 'selection must be [terms, generators]'
+    words = max(1, (g + 63) // 64)
+    bits = np.zeros((t, words * 64), dtype=np.uint8)
+    bits[:, :g] = selection
+    sel = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder='little')).view('<u8').reshape(t, words)
+    signs = np.zeros(t, dtype=np.int8)
+    check(_lib.lib().symgpu_noncon_signs_dev(terms.handle, gens.handle, addr(sel), words, addr(signs)))
+    return signs
+
+
+def noncon_search(coeff, masks, clique, n_free, n_cliques, want_energies=False, want_info=False):
+    """Brute-force minimum of the noncontextual objective over all 2^n_free assignments (``symgpu_noncon_search``): ``coeff`` float64[T],
+    ``masks`` uint64[T] (bit b <=> free generator n_free-1-b), ``clique`` int32[T] (-1 outside the cliques).  Returns (energy, mask), then the
+    float64[2^n_free] energies if ``want_energies`` (n_free <= 24), then the call's info words (L, blocks, entries a block, workgroups) if
+    ``want_info``; among equal energies the largest mask wins."""
+    coeff = np.ascontiguousarray(coeff, dtype=np.float64)
+    masks = np.ascontiguousarray(masks, dtype=np.uint64)
+    clique = np.ascontiguousarray(clique, dtype=np.int32)
+    assert coeff.ndim == 1 and masks.shape == coeff.shape and clique.shape == coeff.shape, 'coeff, masks and clique must be [T]'
+    assert not want_energies or n_free <= 24, 'the full landscape is returned up to 24 free generators'
+    energy, best = ctypes.c_double(0.0), ctypes.c_uint64(0)
+    energies = np.empty(1 << n_free, dtype=np.float64) if want_energies else None
+    info = np.zeros(4, dtype=np.int64)
+    check(_lib.lib().symgpu_noncon_search(addr(coeff), addr(masks), addr(clique), coeff.shape[0], int(n_free), int(n_cliques),
+                                          ctypes.addressof(energy), ctypes.addressof(best), addr(energies), addr(info)))
+    out = (energy.value, best.value)
+    if want_energies:
+        out += (energies,)
+    if want_info:
+        out += (info,)
+    return out
+
+
 def mul_allpairs(inner, ci, outer, co, inner_is_left=True):
     """Uncleaned product: row ``o*Ni + i`` = ``inner[i] ^ outer[o]`` with its phase-corrected coefficient."""
     inner, outer, ci, co = _rows(inner), _rows(outer), _coeff(ci), _coeff(co)

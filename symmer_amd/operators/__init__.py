@@ -5,3 +5,4 @@ from .utils import (symplectic_cleanup, matmul_GF2, mul_symplectic, _rref_binary
 from .base import PauliwordOp
 from .independent_op import IndependentOp
 from .quantum_state import QuantumState, single_term_expval, term_expvals
+from .noncontextual_op import NoncontextualOp, NoncontextualSolver
