@@ -162,13 +162,19 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
     /* 53 / 54: one per call in LDS, one per chunk of workgroups whose slots fit the scratch limit otherwise.
      * tests/test_gpu_csr_families.py asserts through them which form a shape took and in how many launches. */ \
     X(CSR_FILL_LDS, 53, "launches of the fill kernel of symgpu_to_csr_fill (k_csr_fill) with its slots in LDS") \
-    X(CSR_FILL_SCRATCH, 54, "launches of the fill kernel of symgpu_to_csr_fill (k_csr_fill) with its slots in global scratch")
+    X(CSR_FILL_SCRATCH, 54, "launches of the fill kernel of symgpu_to_csr_fill (k_csr_fill) with its slots in global scratch") \
+    /* 55 / 56: the cached device allocator (alloc.hip).  tests/test_gpu_handle_balance.py asserts through them that a call returns every
+     * block it took: 55 is the same before and after, 56 does not move. */ \
+    X(DEV_BLOCKS_LIVE, 55, "a GAUGE, not a count: device blocks handed out by the allocator and not yet returned to it (operators, their " \
+      "caches, scratch, what the contexts keep); never below 0") \
+    X(DEV_FREE_UNKNOWN, 56, "blocks returned to the allocator that it did not hold (a double free, a pointer from elsewhere); the call " \
+      "fails with SYMGPU_E_INVALID and nothing is released")
 #define SYMGPU_COUNTER_ENUM_ENTRY(name, id, text) SYMGPU_CTR_##name = id,
-typedef enum symgpu_counter { SYMGPU_COUNTER_LIST(SYMGPU_COUNTER_ENUM_ENTRY) SYMGPU_CTR_COUNT = 55 } symgpu_counter;
+typedef enum symgpu_counter { SYMGPU_COUNTER_LIST(SYMGPU_COUNTER_ENUM_ENTRY) SYMGPU_CTR_COUNT = 57 } symgpu_counter;
 #undef SYMGPU_COUNTER_ENUM_ENTRY
 /* *value = the counter `which` (an id of the list above; SYMGPU_E_INVALID outside it).  Needs no device and no context. */
 int symgpu_debug_counter(int which, int64_t *value);
-/* The name of counter `which` as spelled in the list ("HASH_RESEEDS", ...), NULL outside 0 .. 54: a binder builds its name -> id map from
+/* The name of counter `which` as spelled in the list ("HASH_RESEEDS", ...), NULL outside 0 .. 56: a binder builds its name -> id map from
  * it instead of copying numbers.  Needs no device and no context. */
 const char *symgpu_debug_counter_name(int which);
 /* The radix sort and the two scans that everything else stands on, run directly on device buffers of the caller's (symgpu_dev_alloc /

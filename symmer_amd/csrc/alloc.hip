@@ -95,6 +95,7 @@ static void canary_check(void *p, size_t bytes) {
 // file block `p` as in use (under g_alloc_mu); returns p
 static void *record_live(void *p, const LiveBlock &blk) {
     g_live[p] = blk;
+    bump_counter(SYMGPU_CTR_DEV_BLOCKS_LIVE);
     if (canary_on()) canary_set(p, blk.req);
     return p;
 }
@@ -153,11 +154,13 @@ int dev_free(void *ptr) {
     std::lock_guard<std::mutex> lk(g_alloc_mu);
     auto it = g_live.find(ptr);
     if (it == g_live.end()) {
+        bump_counter(SYMGPU_CTR_DEV_FREE_UNKNOWN);
         set_error("dev_free: unknown pointer");
         return SYMGPU_E_INVALID;
     }
     const LiveBlock blk = it->second;
     g_live.erase(it);
+    bump_counter(SYMGPU_CTR_DEV_BLOCKS_LIVE, -1);
     if (canary_on()) canary_check(ptr, blk.req);
     DevAlloc &A = g_alloc[blk.dev];                    // the OWNING device's lists (a handle may be dropped while another device is current)
     if (blk.chunk >= 0) {                              // arena block: parked, whatever the limit says (it cannot go back on its own)

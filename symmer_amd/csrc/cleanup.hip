@@ -366,13 +366,9 @@ int cleanup_finish(u32 *markbits_p, const double *sum_of_p, i64 T, bool pair, co
     const i64 n_words = (T + 31) / 32;
     Scratch &wordprefix = pre.wordprefix, &total = pre.total;
     const i64 n_out = pre.n_out;
-    symgpu_op_t res = nullptr;
-    SG_TRY(symgpu_op_alloc(n_out > 0 ? n_out : 1, Wq_out, 1, &res));
-    res->T = n_out;
-    if (want_first) {
-        const int rcf = dev_alloc((size_t)(n_out > 0 ? n_out : 1) * 8, (void **)&res->first);
-        if (rcf != SYMGPU_OK) { symgpu_op_free(res); return rcf; }
-    }
+    OwnedOp res;
+    SG_TRY(res.alloc(rows_or_one(n_out), n_out, Wq_out, true));
+    if (want_first) SG_TRY(res.attach_first());
     if (n_out > 0) {
         const int Wq = W / 2;
         const int wsh = (Wq & (Wq - 1)) == 0 ? __builtin_ctz((unsigned)Wq) : -1;
@@ -408,8 +404,7 @@ int cleanup_finish(u32 *markbits_p, const double *sum_of_p, i64 T, bool pair, co
         const i64 EMIT_BATCH_WORDS = emit_batch_words();
         const i64 bw = n_words < EMIT_BATCH_WORDS ? n_words : EMIT_BATCH_WORDS;
         Scratch meta;
-        int rc = meta.alloc((size_t)bw * 32 * sizeof(uint2));
-        if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
+        SG_TRY(meta.alloc((size_t)bw * 32 * sizeof(uint2)));
         int wpw = 64;                                            // bitmap words per wavefront: aim at >= 16k wavefronts per batch
         while (wpw > 1 && (bw + wpw - 1) / wpw < 16384) wpw >>= 1;
         for (i64 w0 = 0; w0 < n_words; w0 += EMIT_BATCH_WORDS) {
@@ -433,12 +428,11 @@ int cleanup_finish(u32 *markbits_p, const double *sum_of_p, i64 T, bool pair, co
 #undef LAUNCH_STREAM
         }
         }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);   // the scratch buffers are freed on return; keep ordering simple
-        if (e != hipSuccess) { symgpu_op_free(res); return hip_fail(e, "cleanup emit", __FILE__, __LINE__); }
+        KERNEL_CHECK();
+        HIP_TRY(hipStreamSynchronize(st));                   // the scratch buffers are freed on return; keep ordering simple
     }
     res->dup_free = 1;                                          // merged: no two equal rows
-    *out = res;
+    res.hand_out(out);
     return SYMGPU_OK;
 }
 

@@ -109,9 +109,10 @@ static int cleanup_run(const CleanupRequest &rq, symgpu_op_t *out) {
         return SYMGPU_E_INVALID;
     }
     if (rq.T == 0) {
-        symgpu_op_t res = nullptr;
-        SG_TRY(symgpu_op_alloc(1, rq.Wq_out, 1, &res));
-        res->T = 0; res->dup_free = 1; *out = res;
+        OwnedOp res;
+        SG_TRY(res.alloc(1, 0, rq.Wq_out, true));
+        res->dup_free = 1;
+        res.hand_out(out);
         return SYMGPU_OK;
     }
     CleanupRun r;
@@ -182,6 +183,17 @@ int cleanup_pairs(const PairOperands &p, double thr, int use_thr, symgpu_op_t *o
     return cleanup_run(rq, out);
 }
 
+// the tail of the calls that take and return host arrays: *n_out, the capacity check (`what`: the call's words for it), the download
+int finish_to_host(OwnedOp &res, const char *what, uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out) {
+    if (n_out) *n_out = res->T;
+    if (res->T > capacity) {
+        set_error("%s %lld < %lld rows", what, (long long)capacity, (long long)res->T);
+        return SYMGPU_E_CAPACITY;
+    }
+    if (res->T > 0) SG_TRY(symgpu_op_download(res.op, out_rows, out_coeff, capacity));
+    return SYMGPU_OK;
+}
+
 }  // namespace symgpu
 
 using namespace symgpu;
@@ -246,30 +258,16 @@ int symgpu_op_first_index(symgpu_op_t op, uint64_t *first_host, int64_t capacity
     return SYMGPU_OK;
 }
 
-static int finish_to_host(symgpu_op_t res, uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out) {
-    if (n_out) *n_out = res->T;
-    int rc = SYMGPU_OK;
-    if (res->T > capacity) {
-        set_error("output capacity %lld < %lld rows", (long long)capacity, (long long)res->T);
-        rc = SYMGPU_E_CAPACITY;
-    } else if (res->T > 0) {
-        rc = symgpu_op_download(res, out_rows, out_coeff, capacity);
-    }
-    symgpu_op_free(res);
-    return rc;
-}
-
 int symgpu_cleanup(const uint64_t *rows, const double *coeff, int64_t T, int W, double thr, int use_thr, uint64_t *out_rows,
                    double *out_coeff, int64_t capacity, int64_t *n_out) {
     SG_ENTER();
     SG_REQUIRE(T >= 0 && W >= 2 && (W % 2) == 0 && capacity >= 0, "cleanup: sizes (W must be 2*Wq)");
     SG_REQUIRE(T == 0 || (rows && coeff), "cleanup: null input");
-    symgpu_op_t in = nullptr, res = nullptr;
-    SG_TRY(symgpu_op_upload(rows, coeff, T, W / 2, &in));
-    int rc = cleanup_rows(in->rows, in->coeff, T, W, thr, use_thr, &res, W / 2);
-    symgpu_op_free(in);
-    if (rc != SYMGPU_OK) return rc;
-    return finish_to_host(res, out_rows, out_coeff, capacity, n_out);
+    OwnedOp in, res;
+    SG_TRY(symgpu_op_upload(rows, coeff, T, W / 2, in.slot()));
+    SG_TRY(cleanup_rows(in->rows, in->coeff, T, W, thr, use_thr, res.slot(), W / 2));
+    in.reset();
+    return finish_to_host(res, "output capacity", out_rows, out_coeff, capacity, n_out);
 }
 
 int symgpu_mul_cleanup(const uint64_t *inner, const double *ci, int64_t Ni, const uint64_t *outer, const double *co, int64_t No,
@@ -279,13 +277,12 @@ int symgpu_mul_cleanup(const uint64_t *inner, const double *ci, int64_t Ni, cons
     SG_REQUIRE(Ni >= 0 && No >= 0 && Wq >= 1 && capacity >= 0, "mul_cleanup: sizes");
     if (Ni == 0 || No == 0) { if (n_out) *n_out = 0; return SYMGPU_OK; }
     SG_REQUIRE(inner && outer && ci && co, "mul_cleanup: null input");
-    symgpu_op_t a = nullptr, b = nullptr, res = nullptr;
-    int rc = symgpu_op_upload(inner, ci, Ni, Wq, &a);
-    if (rc == SYMGPU_OK) rc = symgpu_op_upload(outer, co, No, Wq, &b);
-    if (rc == SYMGPU_OK) rc = symgpu_mul_cleanup_dev(a, b, inner_is_left, thr, use_thr, &res);
-    symgpu_op_free(a); symgpu_op_free(b);
-    if (rc != SYMGPU_OK) return rc;
-    return finish_to_host(res, out_rows, out_coeff, capacity, n_out);
+    OwnedOp a, b, res;
+    SG_TRY(symgpu_op_upload(inner, ci, Ni, Wq, a.slot()));
+    SG_TRY(symgpu_op_upload(outer, co, No, Wq, b.slot()));
+    SG_TRY(symgpu_mul_cleanup_dev(a.op, b.op, inner_is_left, thr, use_thr, res.slot()));
+    a.reset(); b.reset();
+    return finish_to_host(res, "output capacity", out_rows, out_coeff, capacity, n_out);
 }
 
 }  // extern "C"

@@ -224,6 +224,31 @@ struct symgpu_op_s {
 
 namespace symgpu {
 
+// What Scratch is for buffers, for operator handles: the one owner of a handle the library made for itself (symgpu_op_alloc, or adopted
+// from symgpu_op_upload, cleanup_rows, cleanup_pairs, a nested symgpu_*_dev call).  The handle is freed when the owner goes unless it was
+// handed out, so every error return may be a plain HIP_TRY / SG_TRY.  An error path may thus release a handle that queued work still
+// uses, as ~Scratch does: a device's calls run on one stream, and dev_free only parks the block for a later call on that stream.
+// No copies, no sharing: a handle has one owner at a time.
+struct OwnedOp {
+    symgpu_op_t op = nullptr;
+    OwnedOp() {}
+    ~OwnedOp() { reset(); }
+    OwnedOp(const OwnedOp &) = delete;
+    OwnedOp &operator=(const OwnedOp &) = delete;
+    void reset() { if (op) symgpu_op_free(op); op = nullptr; }
+    void adopt(symgpu_op_t fresh) { reset(); op = fresh; }
+    symgpu_op_t *slot() { reset(); return &op; }                          // where a callee that makes a fresh handle puts it
+    int alloc(i64 capacity, i64 T, int Wq, bool with_coeff) { SG_TRY(symgpu_op_alloc(capacity, Wq, with_coeff, slot())); op->T = T; return SYMGPU_OK; }
+    symgpu_op_t release() { symgpu_op_t h = op; op = nullptr; return h; }
+    void hand_out(symgpu_op_t *out) { *out = release(); }
+    // the buffers that go with the handle (op_invalidate frees them): cached row hashes / first-occurrence indices of `capacity` rows
+    int attach_hash() { return dev_alloc((size_t)op->capacity * 8 + 16, (void **)&op->hash); }
+    int attach_first() { return dev_alloc((size_t)op->capacity * 8, (void **)&op->first); }
+    symgpu_op_s *operator->() const { return op; }
+    explicit operator bool() const { return op != nullptr; }
+};
+constexpr i64 rows_or_one(i64 n) { return n > 0 ? n : 1; }                // the capacity of a result of n rows: never an empty block
+
 // layout.hip — word-major ("bit-sliced column") copy: out[w][t], t padded to Tpad (zero filled)
 int to_wordmajor(const u64 *rows, i64 T, int W, u64 *out, i64 Tpad, hipStream_t st = nullptr);
 // cached word-major copy of a whole operator (padded to a multiple of `mult` terms); built on the main stream
@@ -321,6 +346,8 @@ struct PairOperands {
 // *out is a fresh operator with the cleaned result; want_first: it carries symgpu_op_s::first
 int cleanup_rows(const u64 *rows, const double *coeff, i64 T, int W, double thr, int use_thr, symgpu_op_t *out, int Wq_out, bool want_first = false);
 int cleanup_pairs(const PairOperands &p, double thr, int use_thr, symgpu_op_t *out, bool want_first = false);
+// the tail of the calls that take and return host arrays: *n_out, the capacity check (`what`: the call's words for it), the download
+int finish_to_host(OwnedOp &res, const char *what, uint64_t *out_rows, double *out_coeff, int64_t capacity, int64_t *n_out);
 
 // pair_dups.hip — the pairs of a product whose 64-bit key another pair shares, found without sorting the keys
 bool pair_dups_fits(i64 Ni, i64 No, bool squared, i64 Tk, int *B_out, int *sb_out = nullptr);      // host-side: would pair_dups_dev take this product?

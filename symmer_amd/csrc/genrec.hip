@@ -122,23 +122,18 @@ int symgpu_generators_dev(symgpu_op_t op, symgpu_op_t *out) {
     for (i64 r = 0; r < (i64)piv.size(); ++r)
         if (piv[r] >= 0) keep.push_back(r);                       // a row that is non-zero after the reduction owns a pivot, and vice versa
     const i64 k = (i64)keep.size();
-    symgpu_op_t res = nullptr;
-    SG_TRY(symgpu_op_alloc(k > 0 ? k : 1, op->Wq, 1, &res));
-    res->T = k;
+    OwnedOp res;
+    SG_TRY(res.alloc(rows_or_one(k), k, op->Wq, true));
     if (k > 0) {
         Scratch idx;
-        int rc = idx.alloc((size_t)k * 8);
-        if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
-        hipError_t e = hipMemcpyAsync(idx.p, keep.data(), (size_t)k * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_gather_ones, dim3((unsigned)((k * W + 255) / 256)), dim3(256), 0, st, work.as<u64>(), W, idx.as<i64>(), k, res->rows, res->coeff);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);          // `keep` and `idx` end here
-        if (e != hipSuccess) { symgpu_op_free(res); return hip_fail(e, "generators_dev", __FILE__, __LINE__); }
+        SG_TRY(idx.alloc((size_t)k * 8));
+        HIP_TRY(hipMemcpyAsync(idx.p, keep.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_gather_ones, dim3((unsigned)((k * W + 255) / 256)), dim3(256), 0, st, work.as<u64>(), W, idx.as<i64>(), k, res->rows, res->coeff);
+        KERNEL_CHECK();
+        HIP_TRY(hipStreamSynchronize(st));                          // `keep` and `idx` end here
     }
     res->dup_free = 1;                                              // reduced rows with distinct pivots are distinct
-    *out = res;
+    res.hand_out(out);
     return SYMGPU_OK;
 }
 

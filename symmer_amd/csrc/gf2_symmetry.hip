@@ -112,11 +112,9 @@ int symgpu_symmetry_kernel(const uint64_t *H, int64_t M, int n_qubits, int Wq, u
     SG_ENTER();
     SG_REQUIRE(M >= 0 && n_qubits >= 1 && Wq == (n_qubits + 63) / 64 && k, "symmetry_kernel: sizes");
     SG_REQUIRE(H || M == 0, "symmetry_kernel: null input");
-    symgpu_op_t op = nullptr;
-    SG_TRY(symgpu_op_upload(H, nullptr, M, Wq, &op));
-    int rc = symgpu_symmetry_kernel_dev(op, n_qubits, out, capacity, k, xor_count);
-    symgpu_op_free(op);
-    return rc;
+    OwnedOp op;
+    SG_TRY(symgpu_op_upload(H, nullptr, M, Wq, op.slot()));
+    return symgpu_symmetry_kernel_dev(op.op, n_qubits, out, capacity, k, xor_count);
 }
 
 }  // extern "C"

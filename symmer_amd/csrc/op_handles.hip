@@ -124,16 +124,6 @@ int symgpu_op_free(symgpu_op_t op) {
     return SYMGPU_OK;
 }
 
-// a fresh handle of T rows on the current device, freed again unless it is handed out
-namespace {
-struct FreshOp {
-    symgpu_op_t op = nullptr;
-    ~FreshOp() { if (op) symgpu_op_free(op); }
-    int alloc(i64 T, int Wq, bool with_coeff) { SG_TRY(symgpu_op_alloc(T, Wq, with_coeff, &op)); op->T = T; return SYMGPU_OK; }
-    void hand_out(symgpu_op_t *out) { *out = op; op = nullptr; }
-};
-}  // namespace
-
 int symgpu_op_set_rows(symgpu_op_t op, int64_t T) {
     SG_ENTER(op);
     SG_REQUIRE(op && T >= 0 && T <= op->capacity, "op_set_rows");
@@ -189,13 +179,12 @@ int symgpu_op_copy_rows(symgpu_op_t dst, int64_t dst_offset, symgpu_op_t src, in
 int symgpu_op_upload(const uint64_t *rows, const double *coeff, int64_t T, int Wq, symgpu_op_t *out) {
     SG_ENTER();
     SG_REQUIRE(out && T >= 0 && Wq >= 1 && (rows || T == 0), "op_upload");
-    FreshOp f;
-    SG_TRY(f.alloc(T, Wq, coeff != nullptr));
+    OwnedOp f;
+    SG_TRY(f.alloc(T, T, Wq, coeff != nullptr));
     if (T > 0) {
-        hipError_t e = hipMemcpyAsync(f.op->rows, rows, (size_t)T * 2 * Wq * sizeof(u64), hipMemcpyHostToDevice, ctx().stream);
-        if (e == hipSuccess && coeff) e = hipMemcpyAsync(f.op->coeff, coeff, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, ctx().stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);   // host buffers are not retained past the call
-        if (e != hipSuccess) return hip_fail(e, "op_upload memcpy", __FILE__, __LINE__);
+        HIP_TRY(hipMemcpyAsync(f->rows, rows, (size_t)T * 2 * Wq * sizeof(u64), hipMemcpyHostToDevice, ctx().stream));
+        if (coeff) HIP_TRY(hipMemcpyAsync(f->coeff, coeff, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
+        HIP_TRY(hipStreamSynchronize(ctx().stream));                   // host buffers are not retained past the call
         count_h2d((size_t)T * 2 * Wq * sizeof(u64) + (coeff ? (size_t)T * 16 : 0));
         bump_counter(SYMGPU_CTR_OP_UPLOADS);
     }
@@ -231,14 +220,13 @@ int symgpu_op_download(symgpu_op_t op, uint64_t *rows, double *coeff, int64_t ca
 int symgpu_op_clone(symgpu_op_t in, symgpu_op_t *out) {
     SG_ENTER(in);
     SG_REQUIRE(in && out, "op_clone: null argument");
-    FreshOp f;
-    SG_TRY(f.alloc(in->T, in->Wq, in->coeff != nullptr));
+    OwnedOp f;
+    SG_TRY(f.alloc(in->T, in->T, in->Wq, in->coeff != nullptr));
     if (in->T > 0) {
-        hipError_t e = hipMemcpyAsync(f.op->rows, in->rows, (size_t)in->T * 2 * in->Wq * sizeof(u64), hipMemcpyDeviceToDevice, ctx().stream);
-        if (e == hipSuccess && in->coeff) e = hipMemcpyAsync(f.op->coeff, in->coeff, (size_t)in->T * 16, hipMemcpyDeviceToDevice, ctx().stream);
-        if (e != hipSuccess) return hip_fail(e, "op_clone memcpy", __FILE__, __LINE__);
+        HIP_TRY(hipMemcpyAsync(f->rows, in->rows, (size_t)in->T * 2 * in->Wq * sizeof(u64), hipMemcpyDeviceToDevice, ctx().stream));
+        if (in->coeff) HIP_TRY(hipMemcpyAsync(f->coeff, in->coeff, (size_t)in->T * 16, hipMemcpyDeviceToDevice, ctx().stream));
     }
-    f.op->dup_free = in->dup_free;        // the rows are the same rows
+    f->dup_free = in->dup_free;        // the rows are the same rows
     f.hand_out(out);
     return SYMGPU_OK;
 }
@@ -287,21 +275,18 @@ int symgpu_op_upload_bool(const uint8_t *symp, const double *coeff, int64_t T, i
     SG_ENTER();
     SG_REQUIRE(out && T >= 0 && n_qubits >= 1 && (symp || T == 0), "op_upload_bool");
     const int Wq = (n_qubits + 63) / 64;
-    FreshOp f;
-    SG_TRY(f.alloc(T, Wq, coeff != nullptr));
+    OwnedOp f;
+    SG_TRY(f.alloc(T, T, Wq, coeff != nullptr));
     if (T > 0) {
         const size_t nb = (size_t)T * 2 * n_qubits;
         Scratch stage;
         SG_TRY(stage.alloc(nb));
-        hipError_t e = hipMemcpyAsync(stage.p, symp, nb, hipMemcpyHostToDevice, ctx().stream);
-        if (e == hipSuccess && coeff) e = hipMemcpyAsync(f.op->coeff, coeff, (size_t)T * 16, hipMemcpyHostToDevice, ctx().stream);
-        if (e == hipSuccess) {
-            // one wavefront per (row, word): lane l reads the byte of qubit 64 w + l, the ballot is the packed word
-            hipLaunchKernelGGL(k_pack_bool, dim3(bool_grid(T * 2 * Wq)), dim3(256), 0, ctx().stream, stage.as<uint8_t>(), T, n_qubits, Wq, f.op->rows);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);   // host buffers are not retained past the call (and the staging buffer goes)
-        if (e != hipSuccess) return hip_fail(e, "op_upload_bool", __FILE__, __LINE__);
+        HIP_TRY(hipMemcpyAsync(stage.p, symp, nb, hipMemcpyHostToDevice, ctx().stream));
+        if (coeff) HIP_TRY(hipMemcpyAsync(f->coeff, coeff, (size_t)T * 16, hipMemcpyHostToDevice, ctx().stream));
+        // one wavefront per (row, word): lane l reads the byte of qubit 64 w + l, the ballot is the packed word
+        hipLaunchKernelGGL(k_pack_bool, dim3(bool_grid(T * 2 * Wq)), dim3(256), 0, ctx().stream, stage.as<uint8_t>(), T, n_qubits, Wq, f->rows);
+        KERNEL_CHECK();
+        HIP_TRY(hipStreamSynchronize(ctx().stream));                   // host buffers are not retained past the call (and the staging buffer goes)
         count_h2d(nb + (coeff ? (size_t)T * 16 : 0));
         bump_counter(SYMGPU_CTR_OP_UPLOADS);
     }
@@ -341,13 +326,12 @@ int symgpu_op_random(int64_t T, int n_qubits, double density, uint64_t seed, sym
     SG_ENTER();
     SG_REQUIRE(out && T >= 0 && n_qubits >= 1 && density >= 0.0 && density <= 1.0, "op_random");
     int Wq = (n_qubits + 63) / 64;
-    FreshOp f;
-    SG_TRY(f.alloc(T, Wq, true));
+    OwnedOp f;
+    SG_TRY(f.alloc(T, T, Wq, true));
     if (T > 0) {
         u32 th = (u32)(density * 65536.0 + 0.5);
-        hipLaunchKernelGGL(k_random_op, dim3(4096), dim3(256), 0, ctx().stream, f.op->rows, f.op->coeff, T, n_qubits, Wq, th, seed);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "k_random_op", __FILE__, __LINE__);
+        hipLaunchKernelGGL(k_random_op, dim3(4096), dim3(256), 0, ctx().stream, f->rows, f->coeff, T, n_qubits, Wq, th, seed);
+        KERNEL_CHECK();
     }
     f.hand_out(out);
     return SYMGPU_OK;

@@ -71,23 +71,18 @@ int symgpu_op_gather(symgpu_op_t op, const int64_t *idx_host, int64_t n, symgpu_
     SG_REQUIRE(op && out && n >= 0 && (idx_host || n == 0), "op_gather: arguments");
     for (i64 r = 0; r < n; ++r) SG_REQUIRE(idx_host[r] >= 0 && idx_host[r] < op->T, "op_gather: index out of range");
     hipStream_t st = ctx().stream;
-    symgpu_op_t res = nullptr;
-    SG_TRY(symgpu_op_alloc(n > 0 ? n : 1, op->Wq, op->coeff != nullptr, &res));
-    res->T = n;
+    OwnedOp res;
+    SG_TRY(res.alloc(rows_or_one(n), n, op->Wq, op->coeff != nullptr));
     if (n > 0) {
         Scratch idx;
-        int rc = idx.alloc((size_t)n * 8);
-        if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
-        hipError_t e = hipMemcpyAsync(idx.p, idx_host, (size_t)n * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_gather_rows, dim3(grid_of(n * op->Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(op->rows), op->coeff, idx.as<i64>(), n, op->Wq,
-                               reinterpret_cast<u32x4 *>(res->rows), res->coeff);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);          // idx_host is the caller's; idx goes back to the allocator
-        if (e != hipSuccess) { symgpu_op_free(res); return hip_fail(e, "op_gather", __FILE__, __LINE__); }
+        SG_TRY(idx.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpyAsync(idx.p, idx_host, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_gather_rows, dim3(grid_of(n * op->Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(op->rows), op->coeff, idx.as<i64>(), n, op->Wq,
+                           reinterpret_cast<u32x4 *>(res->rows), res->coeff);
+        KERNEL_CHECK();
+        HIP_TRY(hipStreamSynchronize(st));                          // idx_host is the caller's; idx goes back to the allocator
     }
-    *out = res;
+    res.hand_out(out);
     return SYMGPU_OK;
 }
 
@@ -133,69 +128,57 @@ int symgpu_merge_indexed_dev(const symgpu_op_t *parts, int n_parts, int key_bits
     }
     SG_REQUIRE(total < ((i64)1 << 32) - 1, "merge_indexed_dev: too many rows");
     *out = nullptr;
-    symgpu_op_t sorted = nullptr;
-    SG_TRY(symgpu_op_alloc(total > 0 ? total : 1, Wq, 1, &sorted));
-    sorted->T = total;
-    if (total == 0) { sorted->dup_free = 1; *out = sorted; return SYMGPU_OK; }
+    OwnedOp sorted;
+    SG_TRY(sorted.alloc(rows_or_one(total), total, Wq, true));
+    if (total == 0) { sorted->dup_free = 1; sorted.hand_out(out); return SYMGPU_OK; }
     // concatenation (rows, coefficients, keys) and its order by key
     Scratch cat_rows, cat_coeff, keys, keys2, pos, pos2;
-    int rc = cat_rows.alloc((size_t)total * W * 8);
-    if (rc == SYMGPU_OK) rc = cat_coeff.alloc((size_t)total * 16);
-    if (rc == SYMGPU_OK) rc = keys.alloc((size_t)total * 8);
-    if (rc == SYMGPU_OK) rc = keys2.alloc((size_t)total * 8);
-    if (rc == SYMGPU_OK) rc = pos.alloc((size_t)total * 4);
-    if (rc == SYMGPU_OK) rc = pos2.alloc((size_t)total * 4);
-    if (rc != SYMGPU_OK) { symgpu_op_free(sorted); return rc; }
-    hipError_t e = hipSuccess;
+    SG_TRY(cat_rows.alloc((size_t)total * W * 8));
+    SG_TRY(cat_coeff.alloc((size_t)total * 16));
+    SG_TRY(keys.alloc((size_t)total * 8));
+    SG_TRY(keys2.alloc((size_t)total * 8));
+    SG_TRY(pos.alloc((size_t)total * 4));
+    SG_TRY(pos2.alloc((size_t)total * 4));
     i64 at = 0;
-    for (int p = 0; p < n_parts && e == hipSuccess; ++p) {
+    for (int p = 0; p < n_parts; ++p) {
         const i64 T = parts[p]->T;
         if (T == 0) continue;
-        e = hipMemcpyAsync(cat_rows.as<u64>() + at * W, parts[p]->rows, (size_t)T * W * 8, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(cat_coeff.as<double>() + 2 * at, parts[p]->coeff, (size_t)T * 16, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(keys.as<u64>() + at, parts[p]->first, (size_t)T * 8, hipMemcpyDeviceToDevice, st);
+        HIP_TRY(hipMemcpyAsync(cat_rows.as<u64>() + at * W, parts[p]->rows, (size_t)T * W * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(cat_coeff.as<double>() + 2 * at, parts[p]->coeff, (size_t)T * 16, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(keys.as<u64>() + at, parts[p]->first, (size_t)T * 8, hipMemcpyDeviceToDevice, st));
         at += T;
     }
-    if (e != hipSuccess) { symgpu_op_free(sorted); return hip_fail(e, "merge_indexed_dev: concatenation", __FILE__, __LINE__); }
     hipLaunchKernelGGL(k_iota_u32, dim3(grid_of(total)), dim3(256), 0, st, pos.as<u32>(), total);
+    KERNEL_CHECK();
     SortResult by_first;
-    rc = radix_sort({keys.as<u64>(), keys2.as<u64>(), pos.as<u32>(), pos2.as<u32>(), total, 0, sort_bits, nullptr, SortForm::Launches}, &by_first);
-    if (rc != SYMGPU_OK) { symgpu_op_free(sorted); return rc; }
+    SG_TRY(radix_sort({keys.as<u64>(), keys2.as<u64>(), pos.as<u32>(), pos2.as<u32>(), total, 0, sort_bits, nullptr, SortForm::Launches}, &by_first));
     const u64 *ks = by_first.keys;
     const u32 *ps = by_first.vals;
     hipLaunchKernelGGL(k_gather_rows_u32, dim3(grid_of(total * Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(cat_rows.p), cat_coeff.as<double>(), ps, total, Wq,
                        reinterpret_cast<u32x4 *>(sorted->rows), sorted->coeff);
-    e = hipGetLastError();
-    if (e != hipSuccess) { symgpu_op_free(sorted); return hip_fail(e, "merge_indexed_dev: gather", __FILE__, __LINE__); }
+    KERNEL_CHECK();
     if (!do_cleanup) {
         // parts without common rows (the shares of different ranks): the order is all there is to do
-        rc = dev_alloc((size_t)total * 8, (void **)&sorted->first);
-        if (rc != SYMGPU_OK) { symgpu_op_free(sorted); return rc; }
-        e = hipMemcpyAsync(sorted->first, ks, (size_t)total * 8, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { symgpu_op_free(sorted); return hip_fail(e, "merge_indexed_dev", __FILE__, __LINE__); }
+        SG_TRY(sorted.attach_first());
+        HIP_TRY(hipMemcpyAsync(sorted->first, ks, (size_t)total * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
         sorted->dup_free = 1;
-        *out = sorted;
+        sorted.hand_out(out);
         return SYMGPU_OK;
     }
     // rows that several parts share merge at their first occurrence = smallest pair index; sums in pair order of the parts' partial sums
-    symgpu_op_t res = nullptr;
-    rc = cleanup_rows(sorted->rows, sorted->coeff, total, W, thr, use_thr, &res, Wq, true);
-    if (rc == SYMGPU_OK && res->T > 0) {
+    OwnedOp res;
+    SG_TRY(cleanup_rows(sorted->rows, sorted->coeff, total, W, thr, use_thr, res.slot(), Wq, true));
+    if (res->T > 0) {
         // res->first[t] = position in the sorted concatenation -> its pair index
         Scratch g;
-        rc = g.alloc((size_t)res->T * 8);
-        if (rc == SYMGPU_OK) {
-            hipLaunchKernelGGL(k_pick_u64, dim3(grid_of(res->T)), dim3(256), 0, st, ks, res->first, res->T, g.as<u64>());
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(res->first, g.p, (size_t)res->T * 8, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) rc = hip_fail(e, "merge_indexed_dev: indices", __FILE__, __LINE__);
-        }
+        SG_TRY(g.alloc((size_t)res->T * 8));
+        hipLaunchKernelGGL(k_pick_u64, dim3(grid_of(res->T)), dim3(256), 0, st, ks, res->first, res->T, g.as<u64>());
+        KERNEL_CHECK();
+        HIP_TRY(hipMemcpyAsync(res->first, g.p, (size_t)res->T * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
-    symgpu_op_free(sorted);
-    if (rc != SYMGPU_OK) { if (res) symgpu_op_free(res); return rc; }
-    *out = res;
+    res.hand_out(out);
     return SYMGPU_OK;
 }
 

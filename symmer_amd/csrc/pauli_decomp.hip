@@ -414,20 +414,15 @@ static int pd_select_all(const PdPlan &p, const f64x2 *scratch, const u64 *xs, s
         T = t32;
     }
     SG_TRY(pd_require_memory(T * 32, "the operator"));
-    symgpu_op_t op = nullptr;
-    SG_TRY(symgpu_op_alloc((int64_t)T, 1, 1, &op));
-    op->T = (i64)T;
+    OwnedOp op;
+    SG_TRY(op.alloc((i64)T, (i64)T, 1, true));
     op->dup_free = 1;                                    // one term per (x, z)
     if (T > 0) {
         hipLaunchKernelGGL(k_pd_emit, dim3((unsigned)nblk), dim3(256), 0, st, pd_slots(p, scratch, xs), excl.as<u32>(), T, op->rows,
                            reinterpret_cast<f64x2 *>(op->coeff));
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            symgpu_op_free(op);
-            return hip_fail(e, "k_pd_emit", __FILE__, __LINE__);
-        }
+        KERNEL_CHECK();
     }
-    *out = op;
+    op.hand_out(out);
     *n_out = (int64_t)T;
     return SYMGPU_OK;
 }
@@ -470,15 +465,13 @@ static bool pd_basis_in_range(const uint64_t *x, const uint64_t *z, i64 K, int n
 }
 
 static int pd_finish(const PdPlan &p, f64x2 *scratch, const u64 *xs_dev, const PdBasis &basis, symgpu_op_t *out, int64_t *n_out, double *coeff_out, int *form) {
+    OwnedOp all;                                         // the operator of a call without a basis: the caller's once the stream has drained
     if (p.total > 0) SG_TRY(pd_transform(p, scratch));
     if (basis.K > 0) SG_TRY(pd_select_basis(p, scratch, xs_dev, basis.bx.as<u64>(), basis.bz.as<u64>(), basis.K, coeff_out));
-    else SG_TRY(pd_select_all(p, scratch, xs_dev, out, n_out));
+    else SG_TRY(pd_select_all(p, scratch, xs_dev, all.slot(), n_out));
     if (form) *form = p.form;
-    const hipError_t e = hipStreamSynchronize(ctx().stream);
-    if (e != hipSuccess) {
-        if (basis.K == 0 && *out) { symgpu_op_free(*out); *out = nullptr; }
-        return hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    }
+    HIP_TRY(hipStreamSynchronize(ctx().stream));
+    if (basis.K == 0) all.hand_out(out);
     return SYMGPU_OK;
 }
 

@@ -171,14 +171,12 @@ int symgpu_mul_allpairs(const uint64_t *inner, const double *ci, int64_t Ni, con
     SG_REQUIRE(Ni >= 0 && No >= 0 && Wq >= 1, "mul_allpairs: sizes");
     if (Ni == 0 || No == 0) return SYMGPU_OK;
     SG_REQUIRE(inner && outer && ci && co && out_rows && out_coeff, "mul_allpairs: null pointer");
-    symgpu_op_t a = nullptr, b = nullptr, o = nullptr;
-    int rc = symgpu_op_upload(inner, ci, Ni, Wq, &a);
-    if (rc == SYMGPU_OK) rc = symgpu_op_upload(outer, co, No, Wq, &b);
-    if (rc == SYMGPU_OK) rc = symgpu_op_alloc(Ni * No, Wq, 1, &o);
-    if (rc == SYMGPU_OK) rc = symgpu_mul_allpairs_dev(a, b, 0, No, inner_is_left, o);
-    if (rc == SYMGPU_OK) rc = symgpu_op_download(o, out_rows, out_coeff, Ni * No);
-    symgpu_op_free(a); symgpu_op_free(b); symgpu_op_free(o);
-    return rc;
+    OwnedOp a, b, o;
+    SG_TRY(symgpu_op_upload(inner, ci, Ni, Wq, a.slot()));
+    SG_TRY(symgpu_op_upload(outer, co, No, Wq, b.slot()));
+    SG_TRY(o.alloc(Ni * No, 0, Wq, true));
+    SG_TRY(symgpu_mul_allpairs_dev(a.op, b.op, 0, No, inner_is_left, o.op));
+    return symgpu_op_download(o.op, out_rows, out_coeff, Ni * No);
 }
 
 }  // extern "C"

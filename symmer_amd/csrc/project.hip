@@ -171,8 +171,9 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
     *out = nullptr;
     for (int j = 0; j < n_keep; ++j) SG_REQUIRE(keep_qubits[j] >= 0 && keep_qubits[j] < n_qubits && (j == 0 || keep_qubits[j] > keep_qubits[j - 1]), "project_dev: keep_qubits must ascend inside [0, n)");
     if (T == 0) {
-        SG_TRY(symgpu_op_alloc(1, Wq_out, 1, out));
-        (*out)->T = 0;
+        OwnedOp none;
+        SG_TRY(none.alloc(1, 0, Wq_out, true));
+        none.hand_out(out);
         return SYMGPU_OK;
     }
     // source position of every output bit: X half then Z half of the kept qubits
@@ -200,8 +201,9 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
     SG_TRY(read_back_words(total.as<u32>(), 1, nullptr, 0, &n_s));   // also: src / stab_rows / neg_mask are host temporaries of the caller (their copies are ahead in the stream)
     if (n_survived) *n_survived = n_s;
     if (n_s == 0) {
-        SG_TRY(symgpu_op_alloc(1, Wq_out, 1, out));
-        (*out)->T = 0;
+        OwnedOp none;
+        SG_TRY(none.alloc(1, 0, Wq_out, true));
+        none.hand_out(out);
         return SYMGPU_OK;
     }
     SG_TRY(t_rows.alloc((size_t)n_s * W_out * 8));
@@ -246,12 +248,10 @@ int symgpu_noncontextual_dev(symgpu_op_t op, int *is_noncontextual) {
     // np.unique(axis=0) of utils.py:587 = the device cleanup of the bit-packed rows (no threshold); the unique characters partition the
     // non-universal terms into cliques iff no column sits in two of them: every column is in at least one (a term commutes with itself),
     // so iff the set bits of the unique rows add up to the number of columns
-    symgpu_op_t uniq = nullptr;
-    SG_TRY(cleanup_rows(c_rows.as<u64>(), c_coeff.as<double>(), n_nu, W2, 0.0, 0, &uniq, W2 / 2));
+    OwnedOp uniq;
+    SG_TRY(cleanup_rows(c_rows.as<u64>(), c_coeff.as<double>(), n_nu, W2, 0.0, 0, uniq.slot(), W2 / 2));
     uint64_t ones = 0;
-    const int rc = symgpu_op_popcount(uniq, &ones);
-    symgpu_op_free(uniq);
-    if (rc != SYMGPU_OK) return rc;
+    SG_TRY(symgpu_op_popcount(uniq.op, &ones));
     *is_noncontextual = ones == (uint64_t)n_nu ? 1 : 0;
     return SYMGPU_OK;
 }

@@ -110,30 +110,27 @@ static int run_chain(ChainForm form, const ChainRun &c, int *in_b) {
 
 // The operator 0 * I (one identity row, coefficient 0): what the reference's cleanup() makes of an operator without terms (base.py:631-632)
 static int zero_identity_op(int Wq, symgpu_op_t *out) {
-    symgpu_op_t z = nullptr;
-    SG_TRY(symgpu_op_alloc(1, Wq, 1, &z));
+    OwnedOp z;
+    SG_TRY(z.alloc(1, 1, Wq, true));
     hipStream_t st = ctx().stream;
-    hipError_t e = hipMemsetAsync(z->rows, 0, (size_t)2 * Wq * 8, st);
-    if (e == hipSuccess) e = hipMemsetAsync(z->coeff, 0, 16, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { symgpu_op_free(z); return hip_fail(e, "zero_identity_op", __FILE__, __LINE__); }
-    z->T = 1;
-    *out = z;
+    HIP_TRY(hipMemsetAsync(z->rows, 0, (size_t)2 * Wq * 8, st));
+    HIP_TRY(hipMemsetAsync(z->coeff, 0, 16, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    z.hand_out(out);
     return SYMGPU_OK;
 }
 
 // does any row of `op` commute with the row q (host)?  Only asked when a non-Clifford rotation has left no term at all.
 static int any_row_commutes(symgpu_op_t op, const u64 *q_host, bool *any) {
-    symgpu_op_t q = nullptr;
-    SG_TRY(symgpu_op_upload(q_host, nullptr, 1, op->Wq, &q));
+    OwnedOp q;
+    SG_TRY(symgpu_op_upload(q_host, nullptr, 1, op->Wq, q.slot()));
     Scratch flags;
-    int rc = flags.alloc((size_t)op->T);
-    if (rc == SYMGPU_OK) rc = symgpu_commutes_dev(op, 0, op->T, q, flags.as<uint8_t>());
+    SG_TRY(flags.alloc((size_t)op->T));
+    SG_TRY(symgpu_commutes_dev(op, 0, op->T, q.op, flags.as<uint8_t>()));
     uint64_t sum = 0;
-    if (rc == SYMGPU_OK) rc = symgpu_dev_checksum_u8(flags.as<uint8_t>(), op->T, &sum);
-    symgpu_op_free(q);
+    SG_TRY(symgpu_dev_checksum_u8(flags.as<uint8_t>(), op->T, &sum));
     *any = sum != 0;
-    return rc;
+    return SYMGPU_OK;
 }
 
 }  // namespace symgpu
@@ -200,19 +197,17 @@ int symgpu_perform_rotations_dev(symgpu_op_t in, const uint64_t *q_rows_host, co
     SG_ENTER(in);
     SG_REQUIRE(in && out && n_done && clean_out && K >= 0 && (K == 0 || (q_rows_host && cos_t && sin_t && ks_host)), "perform_rotations_dev: null argument");
     const int W = 2 * in->Wq;
-    symgpu_op_t cur = in;                                            // borrowed while cur == in, owned otherwise
-    auto replace = [&](symgpu_op_t next) { if (cur != in) symgpu_op_free(cur); cur = next; };
+    OwnedOp mine;                                                    // the operator after the steps so far; empty while that is still `in`
     *out = nullptr;
     i64 step = 0;
-    int rc = SYMGPU_OK;
-    while (step < K && rc == SYMGPU_OK) {
+    while (step < K) {
+        const symgpu_op_t cur = mine ? mine.op : in;
         if (cur->T == 0) {
             // every rotation is the identity on an operator without terms (np.all of an empty mask, base.py:1130-1133) and the
             // cleanup() that follows it returns 0 * I (base.py:631-632); the next step's cleanup() drops that term again
             symgpu_op_t z = nullptr;
-            rc = zero_identity_op(in->Wq, &z);
-            if (rc != SYMGPU_OK) break;
-            replace(z);
+            SG_TRY(zero_identity_op(in->Wq, &z));
+            mine.adopt(z);
             clean = 0;
             ++step;
             continue;
@@ -223,57 +218,45 @@ int symgpu_perform_rotations_dev(symgpu_op_t in, const uint64_t *q_rows_host, co
             i64 e = step;
             while (e < K && ks_host[e] >= 0) ++e;
             symgpu_op_t res = nullptr;
-            rc = symgpu_rotate_clifford_chain_dev(cur, q_rows_host + step * W, ks_host + step, e - step, &res);
-            if (rc != SYMGPU_OK) break;
-            replace(res);
+            SG_TRY(symgpu_rotate_clifford_chain_dev(cur, q_rows_host + step * W, ks_host + step, e - step, &res));
+            mine.adopt(res);
             step = e;
             continue;
         }
-        symgpu_op_t res = nullptr;
+        OwnedOp res;
         int allc = 1;
-        rc = symgpu_rotate_single_dev(cur, q_rows_host + step * W, cos_t[step], sin_t[step], ks_host[step], thr, &res, &allc);
-        if (rc != SYMGPU_OK) break;
+        SG_TRY(symgpu_rotate_single_dev(cur, q_rows_host + step * W, cos_t[step], sin_t[step], ks_host[step], thr, res.slot(), &allc));
         if (!allc && res && res->T == 0) {
             // The rotation itself has left no term.  Clifford: the rows are vstack([cleaned product, commuting rows]) = none, and the
             // cleanup() after it gives 0 * I.  Non-Clifford: the result is `commute_self + anticom_part` (base.py:1159-1161), an
             // append + cleanup that yields 0 * I when BOTH parts hold no row (then the loop's cleanup() drops its term: no terms) and
             // an operator without terms when commuting rows cancelled each other (then the loop's cleanup() gives 0 * I).
             bool zero_identity = true;
-            if (ks_host[step] < 0) {
-                bool any = false;
-                rc = any_row_commutes(cur, q_rows_host + step * W, &any);
-                if (rc != SYMGPU_OK) { symgpu_op_free(res); break; }
-                zero_identity = any;
-            }
+            if (ks_host[step] < 0) SG_TRY(any_row_commutes(cur, q_rows_host + step * W, &zero_identity));
             if (acted) acted[step] = 1;
             if (zero_identity) {
-                symgpu_op_free(res);
-                res = nullptr;
-                rc = zero_identity_op(in->Wq, &res);
-                if (rc != SYMGPU_OK) break;
+                SG_TRY(zero_identity_op(in->Wq, res.slot()));                // (the empty result goes first)
                 clean = 0;
             } else {
                 clean = 1;                                          // no terms, and the cleanup() of this step has been applied
             }
-            replace(res);
+            mine.adopt(res.release());
             ++step;
             continue;
         }
-        if (!allc) { if (acted) acted[step] = 1; replace(res); }
-        else if (res) symgpu_op_free(res);
+        if (!allc) { if (acted) acted[step] = 1; mine.adopt(res.release()); }
+        else res.reset();
         ++step;
         if (!clean) {
             symgpu_op_t cleaned = nullptr;
-            rc = symgpu_cleanup_dev(cur, thr, 1, &cleaned);          // may leave no term (0 * I, or X + (-X) after an even multiple of pi/2)
-            if (rc != SYMGPU_OK) break;
-            replace(cleaned);
+            SG_TRY(symgpu_cleanup_dev(mine ? mine.op : in, thr, 1, &cleaned));   // may leave no term (0 * I, or X + (-X) after an even multiple of pi/2)
+            mine.adopt(cleaned);
             clean = 1;
         }
     }
-    if (rc != SYMGPU_OK) { if (cur != in) symgpu_op_free(cur); return rc; }
     *n_done = step;
     *clean_out = clean;
-    *out = cur != in ? cur : nullptr;                                // nullptr: the operator is unchanged, keep using `in`
+    mine.hand_out(out);                                              // nullptr: the operator is unchanged, keep using `in`
     return SYMGPU_OK;
 }
 
@@ -289,21 +272,12 @@ int symgpu_rotate_single(const uint64_t *rows, const double *coeff, int64_t N, i
     SG_ENTER();
     SG_REQUIRE(N >= 0 && Wq >= 1 && q_row && all_commute && n_out, "rotate_single: arguments");
     SG_REQUIRE(N == 0 || (rows && coeff), "rotate_single: null input");
-    symgpu_op_t in = nullptr, res = nullptr;
-    SG_TRY(symgpu_op_upload(rows, coeff, N, Wq, &in));
-    int rc = symgpu_rotate_single_dev(in, q_row, cos_t, sin_t, clifford_k, thr, &res, all_commute);
-    symgpu_op_free(in);
-    if (rc != SYMGPU_OK) return rc;
-    if (*all_commute || !res) { *n_out = N; if (res) symgpu_op_free(res); return SYMGPU_OK; }
-    *n_out = res->T;
-    if (res->T > capacity) {
-        set_error("rotate_single: capacity %lld < %lld rows", (long long)capacity, (long long)res->T);
-        rc = SYMGPU_E_CAPACITY;
-    } else {
-        rc = symgpu_op_download(res, out_rows, out_coeff, capacity);
-    }
-    symgpu_op_free(res);
-    return rc;
+    OwnedOp in, res;
+    SG_TRY(symgpu_op_upload(rows, coeff, N, Wq, in.slot()));
+    SG_TRY(symgpu_rotate_single_dev(in.op, q_row, cos_t, sin_t, clifford_k, thr, res.slot(), all_commute));
+    in.reset();
+    if (*all_commute || !res) { *n_out = N; return SYMGPU_OK; }
+    return finish_to_host(res, "rotate_single: capacity", out_rows, out_coeff, capacity, n_out);
 }
 
 int symgpu_rotate_clifford_chain_dev(symgpu_op_t in, const uint64_t *q_rows_host, const int *ks_host, int64_t K, symgpu_op_t *out) {
@@ -318,31 +292,26 @@ int symgpu_rotate_clifford_chain_dev(symgpu_op_t in, const uint64_t *q_rows_host
     const int Wq = in->Wq, W = 2 * Wq;
     *out = nullptr;
     const RotateSwitches sw = read_rotate_switches(true);
-    symgpu_op_t a = nullptr, b = nullptr;
-    SG_TRY(symgpu_op_alloc(T > 0 ? T : 1, Wq, 1, &a));
-    int rc = symgpu_op_alloc(T > 0 ? T : 1, Wq, 1, &b);
-    if (rc == SYMGPU_OK) rc = symgpu_op_copy_rows(a, 0, in, 0, T);
+    OwnedOp a, b;                                                    // the two buffers the forms alternate between; `a` starts as the input
+    SG_TRY(a.alloc(rows_or_one(T), 0, Wq, true));
+    SG_TRY(b.alloc(rows_or_one(T), 0, Wq, true));
+    SG_TRY(symgpu_op_copy_rows(a.op, 0, in, 0, T));
     Scratch qs, ks;
     int in_b = 0;
-    if (rc == SYMGPU_OK && T > 0 && K > 0) {
-        rc = qs.alloc((size_t)K * W * 8);
-        if (rc == SYMGPU_OK) rc = ks.alloc((size_t)K * 4);
-        hipError_t e = hipSuccess;
-        if (rc == SYMGPU_OK) e = hipMemcpyAsync(qs.p, q_rows_host, (size_t)K * W * 8, hipMemcpyHostToDevice, st);
-        if (rc == SYMGPU_OK && e == hipSuccess) e = hipMemcpyAsync(ks.p, ks_host, (size_t)K * 4, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) rc = hip_fail(e, "rotate_clifford_chain_dev", __FILE__, __LINE__);
-        const ChainRun c{in, a, b, T, K, Wq, qs.as<u64>(), ks.as<int>(), ks_host, sw};
-        if (rc == SYMGPU_OK) rc = run_chain(plan_chain(T, Wq, sw), c, &in_b);          // returns with the stream synchronised
-    } else if (rc == SYMGPU_OK) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = hip_fail(e, "rotate_clifford_chain_dev", __FILE__, __LINE__);
+    if (T > 0 && K > 0) {
+        SG_TRY(qs.alloc((size_t)K * W * 8));
+        SG_TRY(ks.alloc((size_t)K * 4));
+        HIP_TRY(hipMemcpyAsync(qs.p, q_rows_host, (size_t)K * W * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ks.p, ks_host, (size_t)K * 4, hipMemcpyHostToDevice, st));
+        const ChainRun c{in, a.op, b.op, T, K, Wq, qs.as<u64>(), ks.as<int>(), ks_host, sw};
+        SG_TRY(run_chain(plan_chain(T, Wq, sw), c, &in_b));          // returns with the stream synchronised
+    } else {
+        HIP_TRY(hipStreamSynchronize(st));
     }
-    if (rc != SYMGPU_OK) { symgpu_op_free(a); symgpu_op_free(b); return rc; }
-    symgpu_op_t res = in_b ? b : a;
-    symgpu_op_free(in_b ? a : b);
+    OwnedOp &res = in_b ? b : a;
     res->T = T;
     res->dup_free = 1;                                              // a permutation of distinct rows XORed with Q on a Q-anticommuting subset
-    *out = res;
+    res.hand_out(out);
     return SYMGPU_OK;
 }
 

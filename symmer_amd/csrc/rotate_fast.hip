@@ -301,22 +301,20 @@ int rotate_join(RotationRun &r, int *done) {
     hipLaunchKernelGGL(k_rotf_scan3, dim3(s.n_blk), dim3(1024), 0, st, s.cls.as<uint8_t>(), T, s.blk.as<u32>(), s.n_blk, s.pself.as<u32>(), s.pnew.as<u32>(),
                        s.cnt.as<RotCounts>(), jt.flags, jt.gen, hcnt_dev);
     KERNEL_CHECK();
-    symgpu_op_t res = nullptr;
-    SG_TRY(symgpu_op_alloc(2 * T, Wq, 1, &res));               // upper bound: no host round trip before the write kernel
-    int rc = dev_alloc((size_t)res->capacity * 8 + 16, (void **)&res->hash);
-    if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
+    OwnedOp res;
+    SG_TRY(res.alloc(2 * T, 0, Wq, true));                     // upper bound: no host round trip before the write kernel
+    SG_TRY(res.attach_hash());
     res->hash_seed = seed;
     launch_rotf_write(in->rows, r.q.as<u64>(), T, Wq, s, res->rows, res->coeff, 0, in->hash, hq, res->hash);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { symgpu_op_free(res); return hip_fail(e, "rotate fast path", __FILE__, __LINE__); }
+    KERNEL_CHECK();
+    HIP_TRY(hipStreamSynchronize(st));
     const RotCounts hc = *hcnt;
-    if (hc.nAnti == 0) { symgpu_op_free(res); if (!hc.dup) in->dup_free = 1; *r.all_commute = 1; *done = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133)
-    if (hc.dup) { symgpu_op_free(res); return SYMGPU_OK; }     // duplicates in the input: general path
+    if (hc.nAnti == 0) { if (!hc.dup) in->dup_free = 1; *r.all_commute = 1; *done = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133): the result is dropped
+    if (hc.dup) return SYMGPU_OK;                              // duplicates in the input: the result is dropped, general path
     res->T = (i64)hc.nC + hc.nA + hc.nN;
     res->dup_free = 1;                 // the input had no duplicates (checked above) and every P^Q that met a row was merged into it
     in->dup_free = 1;
-    *r.out = res;
+    res.hand_out(r.out);
     *r.all_commute = 0;
     *done = 1;
     return SYMGPU_OK;
@@ -332,28 +330,26 @@ int rotate_clifford_fast(RotationRun &r) {
     SG_TRY(s.alloc(T));
     RotCounts *hcnt = nullptr, *hcnt_dev = nullptr;
     SG_TRY(host_counts(&hcnt, &hcnt_dev));
-    symgpu_op_t res = nullptr;
-    SG_TRY(symgpu_op_alloc(T, Wq, 1, &res));                   // a Clifford rotation never adds rows
+    OwnedOp res;
+    SG_TRY(res.alloc(T, 0, Wq, true));                         // a Clifford rotation never adds rows
     // row hashes, if the operand carries them, are handed on (rotated rows: h ^ h(Q)) so that a later non-Clifford rotation or
     // duplicate check of the chain does not hash again
     const u64 *in_hash = (in->hash && ctx().hash_tab && in->hash_seed == ctx().hash_seed) ? in->hash : nullptr;
     u64 hq = 0;
     if (in_hash) {
         hq = host_row_hash(r.q_host, 2 * Wq);
-        const int rc = dev_alloc((size_t)res->capacity * 8 + 16, (void **)&res->hash);
-        if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
+        SG_TRY(res.attach_hash());
         res->hash_seed = in->hash_seed;
     }
     clifford_classify_scan_write(in->rows, in->coeff, r.q.as<u64>(), r.anti.as<u32>(), r.ph.as<uint8_t>(), T, Wq, r.k, r.thr, s, hcnt_dev, res->rows,
                                  res->coeff, in_hash, hq, res->hash);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { symgpu_op_free(res); return hip_fail(e, "rotate Clifford fast path", __FILE__, __LINE__); }
+    KERNEL_CHECK();
+    HIP_TRY(hipStreamSynchronize(st));
     const RotCounts hc = *hcnt;
-    if (hc.nAnti == 0) { symgpu_op_free(res); *r.all_commute = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133)
+    if (hc.nAnti == 0) { *r.all_commute = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133): the result is dropped
     res->T = (i64)hc.nC + hc.nA + hc.nN;
     res->dup_free = in->dup_free;      // distinct rows stay distinct: P^Q anticommutes with Q, so it never meets a commuting row
-    *r.out = res;
+    res.hand_out(r.out);
     *r.all_commute = 0;
     return SYMGPU_OK;
 }

@@ -111,9 +111,8 @@ int rotate_general(RotationRun &r) {
     if (n_comm == T) return SYMGPU_OK;        // every term commutes: identity action (base.py:1131-1133)
     *r.all_commute = 0;
     const i64 n_stack = clifford ? (n_sel + n_comm) : (n_comm + 2 * n_sel);
-    symgpu_op_t stack = nullptr;
-    SG_TRY(symgpu_op_alloc(n_stack > 0 ? n_stack : 1, Wq, 1, &stack));
-    stack->T = n_stack;
+    OwnedOp stack;
+    SG_TRY(stack.alloc(rows_or_one(n_stack), n_stack, Wq, true));
     if (clifford)
         hipLaunchKernelGGL(k_rot_coeff<1>, dim3(grid_for(T)), dim3(256), 0, st, in->coeff, anti, sel.as<u32>(), apos.as<u32>(),
                            cpos.as<u32>(), r.ph.as<uint8_t>(), T, n_sel, n_comm, r.cos_t, r.sin_t, r.k, stack->coeff, dmain.as<u32>(), dprod.as<u32>());
@@ -122,38 +121,29 @@ int rotate_general(RotationRun &r) {
                            cpos.as<u32>(), r.ph.as<uint8_t>(), T, n_sel, n_comm, r.cos_t, r.sin_t, r.k, stack->coeff, dmain.as<u32>(), dprod.as<u32>());
     hipLaunchKernelGGL(k_rot_rows, dim3(grid_for(T * Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(in->rows),
                        reinterpret_cast<const u32x4 *>(r.q.p), T, Wq, dmain.as<u32>(), dprod.as<u32>(), reinterpret_cast<u32x4 *>(stack->rows));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { symgpu_op_free(stack); return hip_fail(e, "rotate build", __FILE__, __LINE__); }
+    KERNEL_CHECK();
     if (clifford && !(r.k & 1)) {
         HIP_TRY(hipStreamSynchronize(st));
         stack->dup_free = in->dup_free;
-        *r.out = stack;
+        stack.hand_out(r.out);
         return SYMGPU_OK;
     }
+    OwnedOp res;
     if (clifford) {
         // (anticom_self * Q) of base.py:1143 = cleanup of the rotated rows: duplicates merged in input order, |sum| > thr kept
         // (the exact factors -i / -1 commute with the IEEE sums); then the commuting rows, untouched (base.py:1151-1154)
-        symgpu_op_t merged = nullptr, res = nullptr;
-        int rc = cleanup_rows(stack->rows, stack->coeff, n_sel, W, r.thr, 1, &merged, Wq);
-        if (rc != SYMGPU_OK) { symgpu_op_free(stack); return rc; }
+        OwnedOp merged;
+        SG_TRY(cleanup_rows(stack->rows, stack->coeff, n_sel, W, r.thr, 1, merged.slot(), Wq));
         const i64 n_merged = merged->T;
-        rc = symgpu_op_alloc(n_merged + n_comm > 0 ? n_merged + n_comm : 1, Wq, 1, &res);
-        if (rc == SYMGPU_OK) rc = symgpu_op_copy_rows(res, 0, merged, 0, n_merged);
-        if (rc == SYMGPU_OK) rc = symgpu_op_copy_rows(res, n_merged, stack, n_sel, n_comm);
-        if (rc == SYMGPU_OK && (e = hipStreamSynchronize(st)) != hipSuccess) rc = hip_fail(e, "rotate Clifford merge", __FILE__, __LINE__);
-        symgpu_op_free(merged);
-        symgpu_op_free(stack);
-        if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
-        res->T = n_merged + n_comm;
+        SG_TRY(res.alloc(rows_or_one(n_merged + n_comm), n_merged + n_comm, Wq, true));
+        SG_TRY(symgpu_op_copy_rows(res.op, 0, merged.op, 0, n_merged));
+        SG_TRY(symgpu_op_copy_rows(res.op, n_merged, stack.op, n_sel, n_comm));
+        HIP_TRY(hipStreamSynchronize(st));
         res->dup_free = in->dup_free;                              // merged rotated rows + the untouched commuting rows
-        *r.out = res;
-        return SYMGPU_OK;
+    } else {
+        SG_TRY(cleanup_rows(stack->rows, stack->coeff, n_stack, W, r.thr, 1, res.slot(), Wq));
     }
-    symgpu_op_t res = nullptr;
-    int rc = cleanup_rows(stack->rows, stack->coeff, n_stack, W, r.thr, 1, &res, Wq);
-    symgpu_op_free(stack);
-    if (rc != SYMGPU_OK) return rc;
-    *r.out = res;
+    res.hand_out(r.out);
     return SYMGPU_OK;
 }
 

@@ -165,9 +165,8 @@ static hipError_t await_report(hipStream_t st, const volatile u64 *host_words, u
 }
 
 // what the report says: a failure (the caller takes the multi-launch paths), the identity action, or the result
-static int finish(ResidentState &s, const RotCounts &hc, symgpu_op_t in, bool clifford, symgpu_op_t res, symgpu_op_t *out, int *all_commute, int *done) {
-    if (hc.dup != 0) {                                                             // verification failed (2), timed out (3), or no report at all (1)
-        symgpu_op_free(res);
+static int finish(ResidentState &s, const RotCounts &hc, symgpu_op_t in, bool clifford, OwnedOp &res, symgpu_op_t *out, int *all_commute, int *done) {
+    if (hc.dup != 0) {                                                             // verification failed (2), timed out (3), or no report at all (1): res goes with its owner
         bump_counter(SYMGPU_CTR_RESIDENT_FAILED);
         if (hc.dup != 2) {                                                         // time-out: arrival counts are in an unknown state
             s.disabled = true; s.epoch = 0;
@@ -180,10 +179,10 @@ static int finish(ResidentState &s, const RotCounts &hc, symgpu_op_t in, bool cl
     }
     *done = 1;
     bump_counter(SYMGPU_CTR_RESIDENT_DONE);
-    if (hc.nAnti == 0) { symgpu_op_free(res); *all_commute = 1; return SYMGPU_OK; }   // identity action (base.py:1131-1133)
+    if (hc.nAnti == 0) { *all_commute = 1; return SYMGPU_OK; }                     // identity action (base.py:1131-1133): res goes with its owner
     res->T = (i64)hc.nC + hc.nA + hc.nN;
     res->dup_free = clifford ? in->dup_free : 1;
-    *out = res;
+    res.hand_out(out);
     *all_commute = 0;
     return SYMGPU_OK;
 }
@@ -224,11 +223,10 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
     }
     s.host_tag = s.host_tag >= 65535 ? 1 : s.host_tag + 1;
     a.host_late = reinterpret_cast<u32 *>(hcnt_dev) + 8; a.host_words = reinterpret_cast<u64 *>(hcnt_dev) + 5; a.host_tag = s.host_tag;
-    symgpu_op_t res = nullptr;
-    SG_TRY(symgpu_op_alloc(clifford ? in->T : 2 * in->T, in->Wq, 1, &res));       // upper bound: no host round trip before the rows are written
+    OwnedOp res;
+    SG_TRY(res.alloc(clifford ? in->T : 2 * in->T, 0, in->Wq, true));             // upper bound: no host round trip before the rows are written
     if (have_hash) {
-        const int rc = dev_alloc((size_t)res->capacity * 8 + 16, (void **)&res->hash);
-        if (rc != SYMGPU_OK) { symgpu_op_free(res); return rc; }
+        SG_TRY(res.attach_hash());
         res->hash_seed = in->hash_seed;
     }
     a.out_rows = reinterpret_cast<u32x4 *>(res->rows); a.out_coeff = res->coeff; a.out_hash = res->hash;
@@ -238,7 +236,7 @@ int rotate_resident_try(symgpu_op_t in, const u64 *q_host, double cos_t, double 
     bump_counter(SYMGPU_CTR_RESIDENT_NS_PREPARE, t_launch - t_enter); bump_counter(SYMGPU_CTR_RESIDENT_NS_LAUNCH, t_wait - t_launch);
     RotCounts hc;
     if (e == hipSuccess) e = await_report(st, host_words, s.host_tag, &hc);
-    if (e != hipSuccess) { symgpu_op_free(res); s.dirty = true; return hip_fail(e, "rotate resident", __FILE__, __LINE__); }
+    if (e != hipSuccess) { s.dirty = true; return hip_fail(e, "rotate resident", __FILE__, __LINE__); }
     bump_counter(SYMGPU_CTR_RESIDENT_NS_WAIT, host_ns() - t_wait);
     return finish(s, hc, in, clifford, res, out, all_commute, done);
 }

@@ -236,8 +236,8 @@ def commutes(a_rows, b_rows):
     return out.view(np.bool_)
 
 
-def commutes_handles(a, b):
-    """bool[N, M] for two device operators (rows only are used): the table is computed into device memory and read back once."""
+def _pair_table_handles(fn, a, b):
+    """uint8[N, M] of the device entry point ``fn(a, 0, N, b, table)``: the table is computed into device memory and read back once."""
     (n, wq, _), (m, wq_b, _) = a.info(), b.info()
     assert wq == wq_b, 'operands packed with different Wq'
     out = np.empty((n, m), dtype=np.uint8)
@@ -245,11 +245,16 @@ def commutes_handles(a, b):
         buf = ctypes.c_void_p()
         check(_lib.lib().symgpu_dev_alloc(n * m, ctypes.byref(buf)))
         try:
-            check(_lib.lib().symgpu_commutes_dev(a.handle, 0, n, b.handle, buf))
+            check(fn(a.handle, 0, n, b.handle, buf))
             check(_lib.lib().symgpu_dev_download(buf, addr(out), n * m))
         finally:
             _lib.lib().symgpu_dev_free(buf)
     return out.view(np.bool_)
+
+
+def commutes_handles(a, b):
+    """bool[N, M] for two device operators (rows only are used): the table is computed into device memory and read back once."""
+    return _pair_table_handles(_lib.lib().symgpu_commutes_dev, a, b)
 
 
 # ---- measurement grouping (csrc/clique.hip) --------------------------------------------------------------------------------------
@@ -261,18 +266,7 @@ CLIQUE_PAIRS, CLIQUE_UNIONS = 1, 2           # SYMGPU_CLIQUE_*: the form of a co
 def qwc_handles(a, b):
     """bool[N, M] for two device operators: True where a's term i and b's term j commute qubit by qubit (``symgpu_qwc_dev``); the table is
     computed into device memory and read back once."""
-    (n, wq, _), (m, wq_b, _) = a.info(), b.info()
-    assert wq == wq_b, 'operands packed with different Wq'
-    out = np.empty((n, m), dtype=np.uint8)
-    if n and m:
-        buf = ctypes.c_void_p()
-        check(_lib.lib().symgpu_dev_alloc(n * m, ctypes.byref(buf)))
-        try:
-            check(_lib.lib().symgpu_qwc_dev(a.handle, 0, n, b.handle, buf))
-            check(_lib.lib().symgpu_dev_download(buf, addr(out), n * m))
-        finally:
-            _lib.lib().symgpu_dev_free(buf)
-    return out.view(np.bool_)
+    return _pair_table_handles(_lib.lib().symgpu_qwc_dev, a, b)
 
 
 def relation_degrees_dev(op, relation):

@@ -565,7 +565,7 @@ def refusal_cases():
     keepalive = (buf, idx_bad, idx_neg, keep_bad, keep_ok, parts)
     cases = [
         # context.hip
-        ('debug_counter/which', 'debug_counter', lambda L, o: L.symgpu_debug_counter(55, byref(n64))),
+        ('debug_counter/which', 'debug_counter', lambda L, o: L.symgpu_debug_counter(57, byref(n64))),
         ('current_device/null', 'current_device', lambda L, o: L.symgpu_current_device(None)),
         ('n_initialised/null', 'n_initialised', lambda L, o: L.symgpu_n_initialised(None)),
         # alloc.hip

@@ -365,24 +365,25 @@ COUNTER_IDS = [
     (43, 'GIVEUP_OPERAND_BUCKET'), (44, 'FLOW_SORTED_WHOLE'), (45, 'FLOW_SORTED_FLAGGED'), (46, 'FLOW_MARKED_FROM_BYTES'),
     (47, 'FLOW_FULL_SORT_REPEAT'), (48, 'PRODUCT_ROWS_ONLY'), (49, 'PRODUCT_PHASE_STREAM'), (50, 'PRODUCT_WIDE_COEFF_THEN_ROWS'),
     (51, 'PRODUCT_WORD_MAJOR_THEN_ROWS'), (52, 'PRODUCT_WORD_MAJOR_BESIDE_ROWS'), (53, 'CSR_FILL_LDS'), (54, 'CSR_FILL_SCRATCH'),
+    (55, 'DEV_BLOCKS_LIVE'), (56, 'DEV_FREE_UNKNOWN'),
 ]
 
 
 def test_debug_counter_ids_and_names_are_frozen():
     """symgpu_debug_counter_name spells exactly the table above (so does the map the Python side builds from it), NULL outside it; every id
-    reads without a device and 55 is the first that does not; an unknown name is a KeyError that names it."""
+    reads without a device and 57 is the first that does not; an unknown name is a KeyError that names it."""
     from symmer_amd import kernels
     lib = _lib.load()
-    assert [i for i, _ in COUNTER_IDS] == list(range(55)) and len({name for _, name in COUNTER_IDS}) == 55
-    got = [(i, lib.symgpu_debug_counter_name(i)) for i in range(55)]
+    assert [i for i, _ in COUNTER_IDS] == list(range(57)) and len({name for _, name in COUNTER_IDS}) == 57
+    got = [(i, lib.symgpu_debug_counter_name(i)) for i in range(57)]
     assert [(i, name.decode('ascii') if name is not None else None) for i, name in got] == COUNTER_IDS
-    assert lib.symgpu_debug_counter_name(-1) is None and lib.symgpu_debug_counter_name(55) is None
+    assert lib.symgpu_debug_counter_name(-1) is None and lib.symgpu_debug_counter_name(57) is None
     assert _lib.counter_ids() == {name: i for i, name in COUNTER_IDS}
     v = ctypes.c_int64(-1)
     for i, name in COUNTER_IDS:
         assert lib.symgpu_debug_counter(i, ctypes.addressof(v)) == _lib.OK and v.value >= 0, name
         assert kernels.counter(name) == v.value
-    assert lib.symgpu_debug_counter(55, ctypes.addressof(v)) == _lib.E_INVALID and lib.symgpu_debug_counter(-1, ctypes.addressof(v)) == _lib.E_INVALID
+    assert lib.symgpu_debug_counter(57, ctypes.addressof(v)) == _lib.E_INVALID and lib.symgpu_debug_counter(-1, ctypes.addressof(v)) == _lib.E_INVALID
     assert kernels.counters(['H2D_BYTES', 'CSR_FILL_SCRATCH']).dtype == np.int64
     with pytest.raises(KeyError, match='no_such'):
         kernels.counter('no_such')
@@ -521,3 +522,31 @@ def test_lock_scan_names_an_entry_point_that_drops_its_lock_and_a_stale_allowlis
     fake = {'x.hip': 'int symgpu_fake(int a) {\n    // SG_ENTER(a); }\n    const char *s = "SG_ENTER( {";\n    return 0;\n}\n'}
     problems, bodies = _lock_violations(fake, {})
     assert list(bodies) == ['symgpu_fake'] and len(problems) == 1, problems
+
+
+# ---- operator handles the library makes for itself have one owner (OwnedOp, common.h) ------------------------------------------------
+# Raw symgpu_op_alloc / symgpu_op_free calls may stand where they are defined and in the owner, nowhere else.
+RAW_HANDLE_CALLS_ALLOWED_IN = ('op_handles.hip', 'common.h')
+
+
+def _raw_handle_calls(sources, allowed=RAW_HANDLE_CALLS_ALLOWED_IN):
+    """'file:line: call' for every symgpu_op_alloc( / symgpu_op_free( in `sources` ({file name: text}) outside `allowed`."""
+    found = []
+    for fname, src in sorted(sources.items()):
+        if fname in allowed:
+            continue
+        for n, line in enumerate(_strip_c_comments_and_strings(src).split('\n'), 1):
+            found += [f'{fname}:{n}: {m.group(1)}(' for m in re.finditer(r'\b(symgpu_op_alloc|symgpu_op_free)\s*\(', line)]
+    return found
+
+
+def test_operator_handles_inside_the_library_go_through_their_owner():
+    csrc = os.path.join(ROOT, 'symmer_amd', 'csrc')
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h'))}
+    assert len(sources) >= 50 and set(RAW_HANDLE_CALLS_ALLOWED_IN) <= set(sources)
+    found = _raw_handle_calls(sources)
+    assert not found, 'raw operator handle calls (use OwnedOp, common.h):\n' + '\n'.join(found)
+    # the owner is where the scan expects it, and the scan sees a call where there is one (comments and strings do not count)
+    assert _raw_handle_calls({'common.h': sources['common.h']}, allowed=()) and 'struct OwnedOp' in sources['common.h']
+    fake = {'x.hip': '// symgpu_op_free(a);\nconst char *s = "symgpu_op_alloc(";\nint f() {\n    return symgpu_op_free (res);\n}\n'}
+    assert _raw_handle_calls(fake) == ['x.hip:4: symgpu_op_free(']
