@@ -418,6 +418,49 @@ typedef struct symgpu_csr_s *symgpu_csr_t;
 int symgpu_to_csr_count(symgpu_op_t op, int n_qubits, int64_t *nnz, int64_t *fill_scratch_bytes, symgpu_csr_t *plan);
 int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *indptr, int index_bytes);
 
+/* ---- f7: H x on a dense statevector without the matrix, and the vector kernels of exact_gs_energy (symmer/utils.py:14-76;
+ * csrc/matvec.hip, csrc/lanczos.hip).  Conventions of f5: qubit 0 is the MOST significant bit of a basis index b; for term k, x_k and z_k
+ * are its X and Z parts as n-bit integers, Y_k = |x_k & z_k|, c'_k = c_k (-i)^{Y_k} (an exact component swap), and
+ *   (H v)[b] = sum_k c'_k (-1)^{|b & z_k|} v[b ^ x_k]
+ * The operator is not cleaned: repeated terms each count.  Vectors are complex128 [2^n] device buffers of symgpu_dev_alloc.
+ * symgpu_matvec_plan   groups the terms of a resident operator (with coefficients, Wq = 1) by X-part on its device and keeps c', z and the
+ *   group table resident in *plan; the operator is not referenced afterwards.  n_qubits 1 .. 32, anything else SYMGPU_E_INVALID before
+ *   anything is allocated.  T = 0 is a valid plan (H = 0).  symgpu_matvec_free frees it; symgpu_matvec_info reports its sizes (any output
+ *   may be NULL): n_groups = the distinct X-parts G, device_bytes = what the plan holds, 20 T + 8 G + 4 (0 for T = 0).
+ * symgpu_matvec_apply   y = H x, x != y.  Summation order, the same on every run (no floating-point atomics; two calls give the same
+ *   bits): row b is  D_0(b) x[b ^ x_0] + D_1(b) x[b ^ x_1] + ...  over the groups in ascending x, the sum started from the first product,
+ *   every product a plain IEEE complex product (re = D.re x.re - D.im x.im, im = D.re x.im + D.im x.re, each operation rounded);
+ *   D_g(b) = sum_{k in g} c'_k (-1)^{|b & z_k|}, the terms of a group in operator order, started from the first term.  T = 0: zeros.
+ *   *form (may be NULL) = SYMGPU_MATVEC_DIRECT: one thread per row, the gathered element read straight from memory (a wavefront's 64 rows
+ *   read 64 consecutive elements); 0 when no kernel ran (T = 0).  It is the only form: none other has been measured to pay, so
+ *   there is no switch.  A workgroup takes 2^8 consecutive rows.
+ * symgpu_matvec_sector_mask   plan_N must have no term with x != 0 (SYMGPU_E_INVALID otherwise); keep_dev uint8 [2^n]: keep[b] = 1 iff
+ *   the nearest integer to Re D_0(b) equals n_particles, else 0; *n_kept = the number of kept states.
+ * symgpu_lanczos_step   basis_dev complex128 [capacity][2^n], slots 0 .. j hold orthonormal vectors, 0 <= j < capacity < 65536.
+ *   w = keep o (H v_j) (keep_dev uint8 [2^n] or NULL); h_i = <v_i, w> for i <= j; *alpha = Re h_j; w <- w - h_0 v_0 - ... - h_j v_j in
+ *   that order; the same again (classical Gram-Schmidt done twice; the second pass does not change alpha); *beta = |w|; if
+ *   j + 1 < capacity and beta > 0, v_{j+1} = w / beta.  All j + 1 inner products of a pass come from one launch over the basis and all
+ *   subtractions from one.  Nothing but the two scalars returns to the host.
+ *   Reductions run in a fixed two-level order: chunks of C = max(256, 2^n / 1024) consecutive elements; within a chunk thread t of 256
+ *   adds the products conj(v[b]) w[b] of elements t, t + 256, ... to 0 in ascending order, and the 256 thread sums are folded by
+ *   halving (s[t] += s[t + 128], then 64, ... 1); one workgroup then adds the chunk sums to 0 in ascending chunk order.
+ * symgpu_vec_combine   out = s_0 v_0 + ... + s_{m-1} v_{m-1} over the first m vectors of basis_dev ([m][2^n]), s_host double [m], the sum
+ *   started from the first product; normalise != 0: then out / |out| (the norm in the order above; a zero vector stays zero).  out may
+ *   be slot 0 of the basis: the restart of the iteration.  The call takes no plan, so it runs on the calling thread's CURRENT device: the
+ *   basis and out must live there.
+ * The device memory is checked before it is allocated (SYMGPU_E_NOMEM); every scratch buffer is freed before a call returns, also on
+ * failure. */
+#define SYMGPU_MATVEC_DIRECT 1
+struct symgpu_matvec_s;   /* a plan: opaque, owned by the caller between symgpu_matvec_plan and symgpu_matvec_free */
+int symgpu_matvec_plan(symgpu_op_t op, int n_qubits, struct symgpu_matvec_s **plan);
+int symgpu_matvec_free(struct symgpu_matvec_s *plan);
+int symgpu_matvec_info(struct symgpu_matvec_s *plan, int *n_qubits, int64_t *n_terms, int64_t *n_groups, int64_t *device_bytes);
+int symgpu_matvec_apply(struct symgpu_matvec_s *plan, const double *x_dev, double *y_dev, int *form /* or NULL */);
+int symgpu_matvec_sector_mask(struct symgpu_matvec_s *plan_N, int64_t n_particles, uint8_t *keep_dev, int64_t *n_kept);
+int symgpu_lanczos_step(struct symgpu_matvec_s *plan, const uint8_t *keep_dev /* or NULL */, double *basis_dev, int64_t capacity, int64_t j,
+                        double *alpha, double *beta);
+int symgpu_vec_combine(const double *basis_dev, int64_t m, int n_qubits, const double *s_host, double *out_dev, int normalise);
+
 /* ---- f6: PauliwordOp.from_matrix (base.py:239-425), the inverse of f5: the Pauli decomposition of a 2^n x 2^n matrix M, n_qubits 1 .. 31
  * (csrc/pauli_decomp.hip).  With the conventions of f5 (qubit 0 the MOST significant bit of b, x, z):
  *   c(x, z) = i^{|x & z| mod 4} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]

@@ -116,6 +116,13 @@ SIGNATURES = {
     'symgpu_to_csr_fill': [P, P, P, P, c_int],
     'symgpu_from_matrix_dense': [P, c_int, P, P, c_i64, PP, P, P, P],
     'symgpu_from_matrix_csr': [P, P, P, c_int, c_i64, c_int, P, P, c_i64, PP, P, P, P],
+    'symgpu_matvec_plan': [P, c_int, PP],
+    'symgpu_matvec_free': [P],
+    'symgpu_matvec_info': [P, P, P, P, P],
+    'symgpu_matvec_apply': [P, P, P, P],
+    'symgpu_matvec_sector_mask': [P, c_i64, P, P],
+    'symgpu_lanczos_step': [P, P, P, c_i64, c_i64, P, P],
+    'symgpu_vec_combine': [P, c_i64, c_int, P, P, c_int],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

@@ -37,6 +37,7 @@ static int csr_grid(i64 n, int block = 256) {
 }
 
 // ---- 1. grouping -------------------------------------------------------------------------------------------------------------
+// (matvec.hip restates k_csr_keys, k_csr_heads and the sort / scan sequence of csr_count for its plan: keep the two in step)
 __global__ __launch_bounds__(256) void k_csr_keys(const u64 *__restrict__ rows, i64 T, int n, u64 *__restrict__ key, u32 *__restrict__ idx) {
     const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;

@@ -697,6 +697,147 @@ def to_csr(devop, n_qubits, index_dtype=None):
     return data, indices, indptr
 
 
+# ---- H x on dense statevectors and the vector kernels of exact_gs_energy (csrc/matvec.hip, csrc/lanczos.hip) --------------------------
+MATVEC_DIRECT = 1                            # SYMGPU_MATVEC_DIRECT: the form a matvec_apply reports (0: no kernel ran, T = 0)
+
+
+class DeviceBuffer:
+    """Owner of a block of ``symgpu_dev_alloc``: ``nbytes`` bytes on the current device, freed by ``free()``, on leaving a ``with`` block
+    or when collected."""
+
+    def __init__(self, nbytes):
+        self.ptr, self.nbytes = ctypes.c_void_p(), int(nbytes)
+        rc = _lib.lib().symgpu_dev_alloc(self.nbytes, ctypes.byref(self.ptr))
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        check(rc)
+
+    @classmethod
+    def upload(cls, array):
+        array = np.ascontiguousarray(array)
+        buf = cls(array.nbytes)
+        buf.write(array)
+        return buf
+
+    def write(self, array):
+        """``array`` to the start of the block."""
+        array = np.ascontiguousarray(array)
+        assert array.nbytes <= self.nbytes
+        check(_lib.lib().symgpu_dev_upload(self.ptr, addr(array), array.nbytes))
+
+    def download(self, dtype, count, offset_bytes=0):
+        out = np.empty(count, dtype=dtype)
+        check(_lib.lib().symgpu_dev_download(ctypes.c_void_p(self.ptr.value + int(offset_bytes)), addr(out), out.nbytes))
+        return out
+
+    def free(self):
+        if self.ptr is not None and self.ptr.value:
+            _lib.load().symgpu_dev_free(self.ptr)
+        self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MatvecPlan:
+    """Owner of a ``symgpu_matvec_plan``: the terms of a device operator of 1 .. 32 qubits grouped by X-part, resident until ``free()``
+    (also on leaving a ``with`` block, or when collected).  The operator itself is not referenced after the constructor returns."""
+
+    def __init__(self, devop, n_qubits):
+        n_qubits = int(n_qubits)
+        if not 1 <= n_qubits <= 32:
+            raise ValueError(f'matvec: n_qubits = {n_qubits} outside 1 .. 32')
+        self.handle = ctypes.c_void_p()
+        rc = _lib.lib().symgpu_matvec_plan(devop.handle, n_qubits, ctypes.byref(self.handle))
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        check(rc)
+        self.n_qubits = n_qubits
+
+    def info(self):
+        """(n_qubits, n_terms, n_groups, device_bytes)."""
+        n, t, g, b = c_int(0), c_i64(0), c_i64(0), c_i64(0)
+        check(_lib.lib().symgpu_matvec_info(self.handle, ctypes.addressof(n), ctypes.addressof(t), ctypes.addressof(g), ctypes.addressof(b)))
+        return n.value, t.value, g.value, b.value
+
+    def apply(self, x, y):
+        """``y = H x`` for two ``DeviceBuffer`` of ``2^n`` complex128 (not the same one); returns the form that ran."""
+        form = c_int(0)
+        check(_lib.lib().symgpu_matvec_apply(self.handle, x.ptr, y.ptr, ctypes.addressof(form)))
+        return form.value
+
+    def matvec(self, v):
+        """``H v`` for a host vector of ``2^n`` numbers: upload, apply, download.  Returns (complex128[2^n], form)."""
+        v = np.ascontiguousarray(v, dtype=np.complex128).reshape(-1)
+        if v.shape[0] != 1 << self.n_qubits:
+            raise ValueError(f'matvec: the vector has {v.shape[0]} elements, 2^{self.n_qubits} wanted')
+        with DeviceBuffer.upload(v) as x, DeviceBuffer(v.nbytes) as y:
+            form = self.apply(x, y)
+            return y.download(np.complex128, v.shape[0]), form
+
+    def sector_mask(self, n_particles, keep):
+        """For the plan of a diagonal operator N: ``keep`` (``DeviceBuffer`` of ``2^n`` bytes) gets 1 where the nearest integer to
+        ``Re N[b, b]`` is ``n_particles``, else 0; returns the number of kept states."""
+        n_kept = c_i64(0)
+        check(_lib.lib().symgpu_matvec_sector_mask(self.handle, int(n_particles), keep.ptr, ctypes.addressof(n_kept)))
+        return n_kept.value
+
+    def lanczos_step(self, keep, basis, capacity, j):
+        """One Lanczos step with full reorthogonalisation on the resident ``basis`` (``DeviceBuffer`` of ``capacity`` vectors, slots
+        0 .. j orthonormal; ``keep``: a sector mask or None): returns (alpha, beta) and leaves ``v_{j+1}`` in slot j + 1 if there is one
+        and beta > 0."""
+        alpha, beta = ctypes.c_double(0), ctypes.c_double(0)
+        rc = _lib.lib().symgpu_lanczos_step(self.handle, None if keep is None else keep.ptr, basis.ptr, int(capacity), int(j),
+                                            ctypes.addressof(alpha), ctypes.addressof(beta))
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        check(rc)
+        return alpha.value, beta.value
+
+    def free(self):
+        if self.handle is not None and self.handle.value:
+            _lib.load().symgpu_matvec_free(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def vec_combine(basis, m, n_qubits, s, out=None, normalise=False):
+    """``out = sum_j s[j] v_j`` over the first ``m`` vectors of ``basis`` (real ``s``), scaled to unit norm with ``normalise``.  ``out``:
+    a ``DeviceBuffer`` of ``2^n`` complex128, or None for slot 0 of the basis (the restart)."""
+    s = np.ascontiguousarray(s, dtype=np.float64)
+    assert s.shape == (int(m),)
+    check(_lib.lib().symgpu_vec_combine(basis.ptr, int(m), int(n_qubits), addr(s), (basis if out is None else out).ptr, 1 if normalise else 0))
+
+
+def mem_info():
+    """(free, total) bytes of the current device."""
+    free_b, total_b = c_i64(0), c_i64(0)
+    check(_lib.lib().symgpu_mem_info(ctypes.addressof(free_b), ctypes.addressof(total_b)))
+    return free_b.value, total_b.value
+
+
 # ---- PauliwordOp.from_matrix: Pauli decomposition on the device (csrc/pauli_decomp.hip) -----------------------------------------------
 PAULI_ONE_PASS, PAULI_TWO_PASS = 1, 2        # SYMGPU_PAULI_ONE_PASS / SYMGPU_PAULI_TWO_PASS: the transform form a call reports
 

@@ -863,6 +863,42 @@ class PauliwordOp:
         data, indices, indptr = kernels.to_csr(self._device(), self.n_qubits)
         return csr_matrix((data, indices, indptr), shape=(side, side))
 
+    def _matvec_plan(self) -> "kernels.MatvecPlan":
+        """The operator's terms grouped by X-part on the device (csrc/matvec.hip), taken as they are (not cleaned)."""
+        if not 1 <= self.n_qubits <= 32:
+            raise ValueError(f'matvec: {self.n_qubits} qubits; 1 .. 32 are supported (a statevector of 2^n complex numbers)')
+        if self.n_terms == 0:
+            with kernels.DeviceOp.alloc(1, 1, True) as empty:
+                empty.set_rows(0)
+                return kernels.MatvecPlan(empty, self.n_qubits)
+        return kernels.MatvecPlan(self._device(), self.n_qubits)
+
+    def matvec(self, v) -> np.ndarray:
+        """``self.to_sparse_matrix @ v`` without the matrix: ``v`` is array-like of ``2^n`` numbers, shape ``(2^n,)`` or ``(2^n, 1)``; the
+        result is complex128 of the same shape.  Row b is ``sum_g D_g(b) v[b ^ x_g]`` over the distinct X-parts of the terms (DESIGN
+        §3.14), summed in a fixed order on the device: the same input gives the same bits.  One call runs plan, upload, apply, download,
+        free; ``as_linear_operator`` keeps the plan for repeated products.  ValueError for a shape mismatch and beyond 32 qubits."""
+        v = np.asarray(v)
+        side = 1 << self.n_qubits
+        if v.shape not in ((side,), (side, 1)):
+            raise ValueError(f'matvec: a vector of shape {v.shape} for an operator of {self.n_qubits} qubits; ({side},) or ({side}, 1) wanted')
+        if self.n_qubits == 0:
+            return (self._c().sum() * v).astype(np.complex128)
+        with self._matvec_plan() as plan:
+            return plan.matvec(v)[0].reshape(v.shape)
+
+    def as_linear_operator(self):
+        """The operator as a ``scipy.sparse.linalg.LinearOperator`` of shape ``(2^n, 2^n)`` and dtype complex128 whose products run on
+        the device (``matvec``): ``eigsh`` and friends work without the CSR matrix.  It holds one plan until it is collected; the
+        operator's later changes do not reach it."""
+        from scipy.sparse.linalg import LinearOperator
+        side = 1 << self.n_qubits
+        if self.n_qubits == 0:
+            c = self._c().sum()
+            return LinearOperator((1, 1), matvec=lambda v: c * np.asarray(v, dtype=np.complex128), dtype=np.complex128)
+        plan = self._matvec_plan()
+        return LinearOperator((side, side), matvec=lambda v: plan.matvec(np.asarray(v).reshape(-1))[0], dtype=np.complex128)
+
     # ---- a10 / f2: GF(2) generator routines (same device kernel as a8) ----------------------------------------
     @cached_property
     def generators(self) -> "PauliwordOp":

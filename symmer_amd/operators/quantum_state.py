@@ -10,6 +10,7 @@ from copy import deepcopy
 from functools import cached_property
 from numbers import Number
 from typing import Dict, List, Union
+import warnings
 import numpy as np
 
 
@@ -52,6 +53,25 @@ class QuantumState:
         bits, coeffs = zip(*state_dict.items())
         coeffs = np.array([complex(*c) if isinstance(c, (tuple, list)) else c for c in coeffs])
         return cls(np.array([[int(i) for i in b] for b in bits]), coeffs)
+
+    @classmethod
+    def from_array(cls, statevector, threshold: float = 1e-15) -> "QuantumState":
+        """base.py:2139-2186: the state of a dense vector of ``2^n`` amplitudes, host NumPy like ``to_sparse_matrix``, whose inverse it
+        is.  A column ``(2^n, 1)`` makes a ket, a row ``(1, 2^n)`` a bra; amplitude ``b`` belongs to the basis string of ``b`` with qubit 0
+        the most significant bit.  The amplitudes with ``|a| >= threshold`` are kept, in ascending index order; a vector that is not
+        normalised only warns."""
+        statevector = np.asarray(statevector)
+        assert len(statevector.shape) == 2 and 1 in statevector.shape, 'state must be a bra (row) or ket (column) vector'
+        vec_type = 'bra' if statevector.shape[0] == 1 else 'ket'
+        statevector = statevector.reshape([-1])
+        n = int(statevector.shape[0]).bit_length() - 1
+        assert statevector.shape[0] == 1 << n, 'the statevector dimension is not a power of 2'
+        if not np.isclose(np.linalg.norm(statevector), 1):
+            warnings.warn('statevector is not normalized')
+        non_zero = np.where(abs(statevector) >= threshold)[0]
+        shifts = np.arange(n - 1, -1, -1, dtype=np.int64)
+        state_matrix = ((non_zero[:, None] >> shifts) & 1).astype(int).reshape(non_zero.shape[0], n)
+        return cls(state_matrix, statevector[non_zero], vec_type=vec_type)
 
     @cached_property
     def to_dictionary(self) -> Dict[str, complex]:
