@@ -45,13 +45,6 @@ __device__ __forceinline__ void tri_pair(u32 p, u32 N, u32 &o, u32 &i) {
 
 constexpr int SUS_RUN_BITS = 16;                                       // the flag pass's partial sort: key bits [32, 48)
 
-static int grid_for(i64 n, int block = 256, int cap = 8192) {
-    i64 g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 // top key bits a radix sort of n keys orders (at most `cap`): ~1-3 % of the keys then share a prefix with another key, which the fix-up
 // passes (cleanup_segments.hip) put in order cheaply
 static int sorted_bits(i64 n, int cap) {

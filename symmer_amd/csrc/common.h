@@ -190,6 +190,20 @@ struct Scratch {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// ---- launch grids ------------------------------------------------------------------------------
+// workgroups of `block` threads for n elements, never none.  grid_for: at most `cap`, for kernels that stride over the grid;
+// grid_each: one thread per element.
+inline int grid_for(i64 n, int block = 256, int cap = 8192) {
+    i64 g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int)g;
+}
+inline unsigned grid_each(i64 n, int block = 256) {
+    const i64 g = (n + block - 1) / block;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+
 }  // namespace symgpu
 
 // ---- device-resident operator ------------------------------------------------------------------
@@ -248,6 +262,12 @@ struct OwnedOp {
     explicit operator bool() const { return op != nullptr; }
 };
 constexpr i64 rows_or_one(i64 n) { return n > 0 ? n : 1; }                // the capacity of a result of n rows: never an empty block
+// a call that is handed a plan instead of an operator runs on the plan's device: the operator-shaped stand-in that SG_ENTER takes
+inline symgpu_op_s scope_of_device(int device) {
+    symgpu_op_s s;
+    s.device = device;
+    return s;
+}
 
 // layout.hip — word-major ("bit-sliced column") copy: out[w][t], t padded to Tpad (zero filled)
 int to_wordmajor(const u64 *rows, i64 T, int W, u64 *out, i64 Tpad, hipStream_t st = nullptr);
@@ -268,9 +288,21 @@ int read_back_wait(ReadBack *rb, u32 *host_out);
 int commutes_dev(const u64 *A, i64 N, const u64 *B, i64 M, int Wq, uint8_t *out, u64 *out_bits, symgpu_op_s *b_owner = nullptr);
 // ycount.hip
 int ycount_dev(const u64 *rows, i64 T, int Wq, int *out);
+// scan.hip — *out = 0 + v[0] + v[1] + ... + v[N - 1], added in that order per component (one wavefront: the order IS the contract)
+int ordered_sum_dev(const f64x2 *v, i64 N, f64x2 *out);
 
 // product.hip, product_pairs.hip, product_driver.hip (what they share among themselves: product_common.h)
 // ---- shared device helpers ----------------------------------------------------------------------
+// first position in the ascending v[0..n) holding a value >= key
+template <typename T, typename I>
+__device__ __forceinline__ I lower_bound(const T *v, I n, u64 key) {
+    I lo = 0, hi = n;
+    while (lo < hi) {
+        const I mid = (lo + hi) >> 1;
+        if ((u64)v[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 // exact phase application: multiply (re, im) by i^e
 __device__ __forceinline__ void apply_phase(double re, double im, int e, double &ore, double &oim) {
     const bool swap = e & 1;

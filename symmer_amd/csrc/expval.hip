@@ -172,25 +172,6 @@ __global__ __launch_bounds__(256) void k_ev_combine(const f64x2 *__restrict__ pa
     prod[k] = f64x2{qr, qi};
 }
 
-// 0 + v[0] + v[1] + ... in term order: one wavefront, 64 values per step through LDS (k_seq_sum of project.hip)
-__global__ __launch_bounds__(64) void k_ev_total(const f64x2 *__restrict__ v, i64 N, f64x2 *__restrict__ out) {
-    __shared__ f64x2 s_p[2][64];
-    const int lane = threadIdx.x;
-    double re = 0.0, im = 0.0;
-    int buf = 0;
-    for (i64 base = 0; base < N; base += 64, buf ^= 1) {
-        if (base + lane < N) s_p[buf][lane] = v[base + lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane == 0) {
-            const int m = (int)(N - base < 64 ? N - base : 64);
-            for (int k = 0; k < m; ++k) { const f64x2 p = s_p[buf][k]; re = __dadd_rn(re, p.x); im = __dadd_rn(im, p.y); }
-        }
-    }
-    if (lane == 0) *out = f64x2{re, im};
-}
-
 template <bool WQ1, bool LDS>
 static void ev_launch(const EvArgs &a, dim3 grid, size_t lds, hipStream_t st) {
     hipLaunchKernelGGL((k_ev_probe<WQ1, LDS>), grid, dim3(256), lds, st, a);
@@ -236,11 +217,11 @@ int symgpu_expval_terms_dev(symgpu_op_t op, symgpu_op_t phi, symgpu_op_t psi, do
     SG_TRY(ensure_hash_tables(ctx().hash_tab ? ctx().hash_seed : 1));
     SG_TRY(hash_rows(phi->rows, S_phi, W, hphi.as<u64>()));
     if (psi != phi) SG_TRY(hash_rows(psi->rows, S_psi, W, hpsi.as<u64>()));
-    hipLaunchKernelGGL(k_ev_xx_rows, dim3((unsigned)((T * Wq + 255) / 256)), dim3(256), 0, st, op->rows, T, Wq, xx.as<u64>());
+    hipLaunchKernelGGL(k_ev_xx_rows, dim3(grid_each(T * Wq)), dim3(256), 0, st, op->rows, T, Wq, xx.as<u64>());
     KERNEL_CHECK();
     SG_TRY(hash_rows(xx.as<u64>(), T, W, hx.as<u64>()));
     HIP_TRY(hipMemsetAsync(table.p, 0, cap * 4, st));
-    hipLaunchKernelGGL(k_ev_insert, dim3((unsigned)((S_phi + 255) / 256)), dim3(256), 0, st, hphi.as<u64>(), S_phi, table.as<u32>(), (u32)(cap - 1));
+    hipLaunchKernelGGL(k_ev_insert, dim3(grid_each(S_phi)), dim3(256), 0, st, hphi.as<u64>(), S_phi, table.as<u32>(), (u32)(cap - 1));
     KERNEL_CHECK();
 
     EvArgs a;
@@ -255,8 +236,8 @@ int symgpu_expval_terms_dev(symgpu_op_t op, symgpu_op_t phi, symgpu_op_t psi, do
     KERNEL_CHECK();
     f64x2 *terms = result.as<f64x2>(), *total = terms + T, *prod = total + 1;
     hipLaunchKernelGGL(k_ev_combine, dim3((unsigned)tiles), dim3(256), 0, st, partial.as<f64x2>(), T, chunks, op->rows, Wq, op->coeff, terms, prod);
-    hipLaunchKernelGGL(k_ev_total, dim3(1), dim3(64), 0, st, prod, T, total);
     KERNEL_CHECK();
+    SG_TRY(ordered_sum_dev(prod, T, total));                         // in term order
     // the one read-back: the total alone through the mailbox, or the terms with the total behind them
     if (!out_terms) {
         u32 w[4] = {0, 0, 0, 0};

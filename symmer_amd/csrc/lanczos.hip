@@ -124,12 +124,12 @@ extern "C" {
 
 int symgpu_lanczos_step(struct symgpu_matvec_s *plan, const uint8_t *keep_dev, double *basis_dev, int64_t capacity, int64_t j, double *alpha, double *beta) {
     SG_REQUIRE(plan, "lanczos_step: null plan");
-    const symgpu_op_s scope_op = matvec_scope(plan);
+    const symgpu_op_s scope_op = scope_of_device(plan->device);
     SG_ENTER(&scope_op);
     SG_REQUIRE(basis_dev && alpha && beta, "lanczos_step: arguments");
     SG_REQUIRE(capacity >= 1 && capacity < ((i64)1 << 16) && j >= 0 && j < capacity, "lanczos_step: 0 <= j < capacity < 65536");
     hipStream_t st = ctx().stream;
-    const u64 N = (u64)1 << plan->n;
+    const u64 N = (u64)1 << plan->xg.n;
     const int nvec = (int)j + 1;
     SG_TRY(matvec_require_memory(N * 16 + (u64)lz_chunks(N) * nvec * 16 + 4096, "a Lanczos step"));
     Scratch w;
@@ -138,7 +138,7 @@ int symgpu_lanczos_step(struct symgpu_matvec_s *plan, const uint8_t *keep_dev, d
     SG_TRY(k.alloc(N, nvec));
     f64x2 *basis = reinterpret_cast<f64x2 *>(basis_dev);
     SG_TRY(matvec_launch(plan, basis + (u64)j * N, w.as<f64x2>(), keep_dev, nullptr));
-    const unsigned grid = (unsigned)((N + LZ_WG - 1) / LZ_WG);
+    const unsigned grid = grid_each((i64)N, LZ_WG);
     for (int pass = 0; pass < 2; ++pass) {                  // classical Gram-Schmidt, twice; alpha is <v_j, w> of the first pass
         SG_TRY(lz_dots(k, basis, N, nvec, w.as<f64x2>(), pass == 0 ? (int)j : -1, 0));
         hipLaunchKernelGGL(k_lz_subtract, dim3(grid), dim3(LZ_WG), 0, st, basis, N, nvec, k.h.as<f64x2>(), w.as<f64x2>());
@@ -168,7 +168,7 @@ int symgpu_vec_combine(const double *basis_dev, int64_t m, int n_qubits, const d
     SG_TRY(s.alloc((size_t)m * 8));
     SG_TRY(k.alloc(N, 1));
     SG_TRY(symgpu_dev_upload(s.p, s_host, m * 8));
-    const unsigned grid = (unsigned)((N + LZ_WG - 1) / LZ_WG);
+    const unsigned grid = grid_each((i64)N, LZ_WG);
     f64x2 *out = reinterpret_cast<f64x2 *>(out_dev);
     hipLaunchKernelGGL(k_lz_combine, dim3(grid), dim3(LZ_WG), 0, st, reinterpret_cast<const f64x2 *>(basis_dev), N, (int)m, s.as<double>(), out);
     KERNEL_CHECK();

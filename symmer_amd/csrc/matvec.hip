@@ -1,66 +1,18 @@
 // matvec.hip — y = H x for a Pauli sum H and a dense statevector x, without the matrix (conventions of sparse_matrix.hip):
 //   y[b] = sum over the groups g of equal X-part, in ascending x_g, of  D_g(b) x[b ^ x_g],
 //   D_g(b) = sum over the terms k of g, in operator order, of  c_k (-i)^{Y_k} (-1)^{|b & z_k|}
-// qubit 0 the MOST significant bit of b, x_k, z_k.  Plan: the grouping of sparse_matrix.hip (key = x as an n-bit integer, stable radix sort
-// of (key, term index), group heads, scan) leaves per sorted term z and c' and per group x and its first term.  Apply: one thread per row,
+// qubit 0 the MOST significant bit of b, x_k, z_k.  Plan: the terms grouped by X-part (xgroups.h), which to_sparse_matrix sums over as
+// well: per sorted term z and c', per group x and its first term.  Apply: one thread per row,
 // the terms read through wave-uniform addresses (scalar loads, every lane the same term), the sign from the parity of b & z, D_g summed
 // from its first term, one gathered read of x per group — the 64 rows of a wavefront read 64 consecutive elements in a permuted order,
 // 1 KiB in whole — one plain IEEE complex product, the row's sum started from its first group.  The next group's element is requested
 // before the current group's terms are summed.  No atomics: a row belongs to one thread.
 #include "matvec.h"
-#include "sort.h"
+#include <memory>
 
 namespace symgpu {
 
 constexpr int MV_TILE = 256;                      // rows per workgroup (64 and 128 measured the same within 4 %)
-
-static unsigned mv_grid(i64 n, int block = 256) {
-    const i64 g = (n + block - 1) / block;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
-// ---- the plan: group the terms by X-part ---------------------------------------------------------------------------------------------
-// k_mv_keys, k_mv_heads and the sort / scan sequence of mv_plan restate k_csr_keys, k_csr_heads and csr_count of sparse_matrix.hip (file-local
-// there): a change of the key or of the order on either side belongs on both.
-__global__ __launch_bounds__(256) void k_mv_keys(const u64 *__restrict__ rows, i64 T, int n, u64 *__restrict__ key, u32 *__restrict__ idx) {
-    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (t >= T) return;
-    key[t] = __brevll(rows[2 * t]) >> (64 - n);
-    idx[t] = (u32)t;
-}
-
-__global__ __launch_bounds__(256) void k_mv_heads(const u64 *__restrict__ key, i64 T, u32 *__restrict__ head) {
-    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= T) return;
-    head[s] = (s == 0 || key[s] != key[s - 1]) ? 1u : 0u;
-}
-
-// c' = c (-i)^Y: exact (a swap and sign flips, no arithmetic)
-__device__ __forceinline__ f64x2 mv_times_minus_i_pow(f64x2 c, int y) {
-    switch (y & 3) {
-        case 0: return c;
-        case 1: return f64x2{c.y, -c.x};
-        case 2: return f64x2{-c.x, -c.y};
-        default: return f64x2{-c.y, c.x};
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mv_terms(const u64 *__restrict__ rows, const double *__restrict__ coeff, const u64 *__restrict__ key,
-                                                  const u32 *__restrict__ idx, const u32 *__restrict__ gexcl, const u32 *__restrict__ head, i64 T, int n,
-                                                  u32 *__restrict__ tz, f64x2 *__restrict__ tc, u32 *__restrict__ gx, u32 *__restrict__ gstart) {
-    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= T) return;
-    const u32 t = idx[s];
-    const u64 x = rows[2 * (i64)t], z = rows[2 * (i64)t + 1];
-    const u32 g = gexcl[s] + head[s] - 1;
-    tz[s] = (u32)(__brevll(z) >> (64 - n));
-    tc[s] = mv_times_minus_i_pow(reinterpret_cast<const f64x2 *>(coeff)[t], __popcll(x & z));
-    if (head[s]) {
-        gx[g] = (u32)key[s];
-        gstart[g] = (u32)s;
-    }
-    if (s == T - 1) gstart[g + 1] = (u32)T;
-}
 
 // ---- y = keep o (H x) ----------------------------------------------------------------------------------------------------------------
 struct MvTerms {
@@ -125,7 +77,8 @@ __global__ __launch_bounds__(256) void k_mv_sector(MvTerms P, long long n_partic
 }
 
 static MvTerms mv_terms_of(const symgpu_matvec_s *p) {
-    return MvTerms{(const u32 *)p->tz, (const f64x2 *)p->tc, (const u32 *)p->gx, (const u32 *)p->gstart, p->G, p->n};
+    const XGroups &g = p->xg;
+    return MvTerms{g.tz.as<u32>(), g.tc.as<f64x2>(), g.gx.as<u32>(), g.gstart.as<u32>(), g.G, g.n};
 }
 
 int matvec_require_memory(u64 bytes, const char *what) {
@@ -144,57 +97,24 @@ int matvec_require_memory(u64 bytes, const char *what) {
 
 int matvec_launch(const symgpu_matvec_s *p, const f64x2 *x, f64x2 *y, const uint8_t *keep, int *form) {
     hipStream_t st = ctx().stream;
-    const u64 N = (u64)1 << p->n;
+    const u64 N = (u64)1 << p->xg.n;
     if (form) *form = 0;
-    if (p->G == 0) {
+    if (p->xg.G == 0) {
         HIP_TRY(hipMemsetAsync(y, 0, (size_t)N * 16, st));
         return SYMGPU_OK;
     }
-    hipLaunchKernelGGL(k_mv_apply, dim3((unsigned)((N + MV_TILE - 1) / MV_TILE)), dim3(MV_TILE), 0, st, mv_terms_of(p), x, y, keep);
+    hipLaunchKernelGGL(k_mv_apply, dim3(grid_each((i64)N, MV_TILE)), dim3(MV_TILE), 0, st, mv_terms_of(p), x, y, keep);
     KERNEL_CHECK();
     if (form) *form = SYMGPU_MATVEC_DIRECT;
     return SYMGPU_OK;
 }
 
-static void mv_release(symgpu_matvec_s *p) {
-    for (void *q : {p->tz, p->tc, p->gx, p->gstart})
-        if (q) dev_free(q);
-    delete p;
-}
-
 static int mv_plan(symgpu_op_t op, int n, symgpu_matvec_s *p) {
-    hipStream_t st = ctx().stream;
     const i64 T = op->T;
-    if (T == 0) return SYMGPU_OK;
     // the sort's buffers (keys, indices, both twice; heads, scan) and the plan's own (z, c', and at most T groups)
-    SG_TRY(matvec_require_memory((u64)T * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 16 + 4 + 4) + 4096, "the plan"));
-    Scratch key, key_tmp, idx, idx_tmp, head, gexcl;
-    SG_TRY(key.alloc((size_t)T * 8));
-    SG_TRY(key_tmp.alloc((size_t)T * 8));
-    SG_TRY(idx.alloc((size_t)T * 4));
-    SG_TRY(idx_tmp.alloc((size_t)T * 4));
-    SG_TRY(head.alloc((size_t)T * 4));
-    SG_TRY(gexcl.alloc((size_t)T * 4 + 4));
-    hipLaunchKernelGGL(k_mv_keys, dim3(mv_grid(T)), dim3(256), 0, st, op->rows, T, n, key.as<u64>(), idx.as<u32>());
-    KERNEL_CHECK();
-    SortResult by_x;
-    SG_TRY(radix_sort({key.as<u64>(), key_tmp.as<u64>(), idx.as<u32>(), idx_tmp.as<u32>(), T, 0, (n + 7) / 8 * 8, nullptr, SortForm::Launches}, &by_x));
-    hipLaunchKernelGGL(k_mv_heads, dim3(mv_grid(T)), dim3(256), 0, st, by_x.keys, T, head.as<u32>());
-    KERNEL_CHECK();
-    u32 *d_total = gexcl.as<u32>() + T;
-    SG_TRY(exclusive_scan_u32(head.as<u32>(), gexcl.as<u32>(), T, d_total));
-    u32 G = 0;
-    SG_TRY(read_back_words(d_total, 1, nullptr, 0, &G));
-    p->G = G;
-    SG_TRY(dev_alloc((size_t)T * 4, &p->tz));
-    SG_TRY(dev_alloc((size_t)T * 16, &p->tc));
-    SG_TRY(dev_alloc((size_t)G * 4, &p->gx));
-    SG_TRY(dev_alloc((size_t)(G + 1) * 4, &p->gstart));
-    p->device_bytes = (i64)T * 20 + (i64)G * 8 + 4;
-    hipLaunchKernelGGL(k_mv_terms, dim3(mv_grid(T)), dim3(256), 0, st, op->rows, op->coeff, by_x.keys, by_x.vals, gexcl.as<u32>(), head.as<u32>(), T, n,
-                       (u32 *)p->tz, (f64x2 *)p->tc, (u32 *)p->gx, (u32 *)p->gstart);
-    KERNEL_CHECK();
-    HIP_TRY(hipStreamSynchronize(st));                        // the operator and the scratch are not referenced once the call has returned
+    if (T > 0) SG_TRY(matvec_require_memory((u64)T * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 16 + 4 + 4) + 4096, "the plan"));
+    SG_TRY(xgroups_build(op, n, false, &p->xg));
+    if (T > 0) HIP_TRY(hipStreamSynchronize(ctx().stream));   // the operator and the scratch are not referenced once the call has returned
     return SYMGPU_OK;
 }
 
@@ -212,41 +132,35 @@ int symgpu_matvec_plan(symgpu_op_t op, int n_qubits, struct symgpu_matvec_s **pl
     SG_REQUIRE(op->Wq == 1, "matvec_plan: the operator's rows have more than one word per half (Wq = 1 wanted)");
     SG_REQUIRE(op->coeff || op->T == 0, "matvec_plan: operator has no coefficients");
     SG_REQUIRE(op->T < ((i64)1 << 31), "matvec_plan: T >= 2^31");
-    symgpu_matvec_s *p = new symgpu_matvec_s();
+    std::unique_ptr<symgpu_matvec_s> p(new symgpu_matvec_s());
     p->device = op->device;
-    p->n = n_qubits;
-    p->T = op->T;
-    const int rc = mv_plan(op, n_qubits, p);
-    if (rc != SYMGPU_OK) {
-        mv_release(p);
-        return rc;
-    }
-    *plan = p;
+    SG_TRY(mv_plan(op, n_qubits, p.get()));
+    *plan = p.release();
     return SYMGPU_OK;
 }
 
 int symgpu_matvec_free(struct symgpu_matvec_s *plan) {
     SG_REQUIRE(plan, "matvec_free: null plan");
-    const symgpu_op_s scope_op = matvec_scope(plan);
+    const symgpu_op_s scope_op = scope_of_device(plan->device);
     SG_ENTER(&scope_op);
-    mv_release(plan);
+    delete plan;
     return SYMGPU_OK;
 }
 
 int symgpu_matvec_info(struct symgpu_matvec_s *plan, int *n_qubits, int64_t *n_terms, int64_t *n_groups, int64_t *device_bytes) {
     SG_REQUIRE(plan, "matvec_info: null plan");
-    const symgpu_op_s scope_op = matvec_scope(plan);
+    const symgpu_op_s scope_op = scope_of_device(plan->device);
     SG_ENTER(&scope_op);
-    if (n_qubits) *n_qubits = plan->n;
-    if (n_terms) *n_terms = plan->T;
-    if (n_groups) *n_groups = plan->G;
-    if (device_bytes) *device_bytes = plan->device_bytes;
+    if (n_qubits) *n_qubits = plan->xg.n;
+    if (n_terms) *n_terms = plan->xg.T;
+    if (n_groups) *n_groups = plan->xg.G;
+    if (device_bytes) *device_bytes = plan->xg.device_bytes();
     return SYMGPU_OK;
 }
 
 int symgpu_matvec_apply(struct symgpu_matvec_s *plan, const double *x_dev, double *y_dev, int *form) {
     SG_REQUIRE(plan, "matvec_apply: null plan");
-    const symgpu_op_s scope_op = matvec_scope(plan);
+    const symgpu_op_s scope_op = scope_of_device(plan->device);
     SG_ENTER(&scope_op);
     if (form) *form = 0;
     SG_REQUIRE(x_dev && y_dev && x_dev != y_dev, "matvec_apply: x and y must be two device buffers");
@@ -257,20 +171,20 @@ int symgpu_matvec_apply(struct symgpu_matvec_s *plan, const double *x_dev, doubl
 
 int symgpu_matvec_sector_mask(struct symgpu_matvec_s *plan_N, int64_t n_particles, uint8_t *keep_dev, int64_t *n_kept) {
     SG_REQUIRE(plan_N, "matvec_sector_mask: null plan");
-    const symgpu_op_s scope_op = matvec_scope(plan_N);
+    const symgpu_op_s scope_op = scope_of_device(plan_N->device);
     SG_ENTER(&scope_op);
     SG_REQUIRE(keep_dev && n_kept, "matvec_sector_mask: arguments");
     *n_kept = 0;
     u32 x0 = 0;
-    if (plan_N->G == 1) SG_TRY(read_back_words((const u32 *)plan_N->gx, 1, nullptr, 0, &x0));
-    SG_REQUIRE(plan_N->G <= 1 && x0 == 0, "matvec_sector_mask: the number operator has a term with an X or a Y");
+    if (plan_N->xg.G == 1) SG_TRY(read_back_words(plan_N->xg.gx.as<u32>(), 1, nullptr, 0, &x0));
+    SG_REQUIRE(plan_N->xg.G <= 1 && x0 == 0, "matvec_sector_mask: the number operator has a term with an X or a Y");
     hipStream_t st = ctx().stream;
-    const u64 N = (u64)1 << plan_N->n;
+    const u64 N = (u64)1 << plan_N->xg.n;
     SG_TRY(matvec_require_memory(4096, "the sector mask"));
     Scratch cnt;
     SG_TRY(cnt.alloc(8));
     HIP_TRY(hipMemsetAsync(cnt.p, 0, 8, st));
-    hipLaunchKernelGGL(k_mv_sector, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, mv_terms_of(plan_N), (long long)n_particles, keep_dev,
+    hipLaunchKernelGGL(k_mv_sector, dim3(grid_each((i64)N)), dim3(256), 0, st, mv_terms_of(plan_N), (long long)n_particles, keep_dev,
                        cnt.as<unsigned long long>());
     KERNEL_CHECK();
     u32 w[2] = {0, 0};

@@ -15,13 +15,6 @@
 
 namespace symgpu {
 
-static int grid_of(i64 n, int block = 256) {
-    i64 g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > (1 << 30)) g = 1 << 30;
-    return (int)g;
-}
-
 // out row r = in row idx[r]: one 16-byte chunk per thread
 __global__ __launch_bounds__(256) void k_gather_rows(const u32x4 *__restrict__ rows, const double *__restrict__ coeff, const i64 *__restrict__ idx, i64 n, int Wq,
                                                       u32x4 *__restrict__ out_rows, double *__restrict__ out_coeff) {
@@ -77,7 +70,7 @@ int symgpu_op_gather(symgpu_op_t op, const int64_t *idx_host, int64_t n, symgpu_
         Scratch idx;
         SG_TRY(idx.alloc((size_t)n * 8));
         HIP_TRY(hipMemcpyAsync(idx.p, idx_host, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gather_rows, dim3(grid_of(n * op->Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(op->rows), op->coeff, idx.as<i64>(), n, op->Wq,
+        hipLaunchKernelGGL(k_gather_rows, dim3(grid_each(n * op->Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(op->rows), op->coeff, idx.as<i64>(), n, op->Wq,
                            reinterpret_cast<u32x4 *>(res->rows), res->coeff);
         KERNEL_CHECK();
         HIP_TRY(hipStreamSynchronize(st));                          // idx_host is the caller's; idx goes back to the allocator
@@ -97,7 +90,7 @@ int symgpu_part_global_index(symgpu_op_t part, const int64_t *inner_idx_host, in
     SG_TRY(oi.alloc((size_t)n_outer * 8));
     HIP_TRY(hipMemcpyAsync(ii.p, inner_idx_host, (size_t)n_inner * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(oi.p, outer_idx_host, (size_t)n_outer * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_global_index, dim3(grid_of(part->T)), dim3(256), 0, st, part->first, part->T, ii.as<i64>(), oi.as<i64>(), Ni_global);
+    hipLaunchKernelGGL(k_global_index, dim3(grid_each(part->T)), dim3(256), 0, st, part->first, part->T, ii.as<i64>(), oi.as<i64>(), Ni_global);
     KERNEL_CHECK();
     HIP_TRY(hipStreamSynchronize(st));
     return SYMGPU_OK;
@@ -148,13 +141,13 @@ int symgpu_merge_indexed_dev(const symgpu_op_t *parts, int n_parts, int key_bits
         HIP_TRY(hipMemcpyAsync(keys.as<u64>() + at, parts[p]->first, (size_t)T * 8, hipMemcpyDeviceToDevice, st));
         at += T;
     }
-    hipLaunchKernelGGL(k_iota_u32, dim3(grid_of(total)), dim3(256), 0, st, pos.as<u32>(), total);
+    hipLaunchKernelGGL(k_iota_u32, dim3(grid_each(total)), dim3(256), 0, st, pos.as<u32>(), total);
     KERNEL_CHECK();
     SortResult by_first;
     SG_TRY(radix_sort({keys.as<u64>(), keys2.as<u64>(), pos.as<u32>(), pos2.as<u32>(), total, 0, sort_bits, nullptr, SortForm::Launches}, &by_first));
     const u64 *ks = by_first.keys;
     const u32 *ps = by_first.vals;
-    hipLaunchKernelGGL(k_gather_rows_u32, dim3(grid_of(total * Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(cat_rows.p), cat_coeff.as<double>(), ps, total, Wq,
+    hipLaunchKernelGGL(k_gather_rows_u32, dim3(grid_each(total * Wq)), dim3(256), 0, st, reinterpret_cast<const u32x4 *>(cat_rows.p), cat_coeff.as<double>(), ps, total, Wq,
                        reinterpret_cast<u32x4 *>(sorted->rows), sorted->coeff);
     KERNEL_CHECK();
     if (!do_cleanup) {
@@ -173,7 +166,7 @@ int symgpu_merge_indexed_dev(const symgpu_op_t *parts, int n_parts, int key_bits
         // res->first[t] = position in the sorted concatenation -> its pair index
         Scratch g;
         SG_TRY(g.alloc((size_t)res->T * 8));
-        hipLaunchKernelGGL(k_pick_u64, dim3(grid_of(res->T)), dim3(256), 0, st, ks, res->first, res->T, g.as<u64>());
+        hipLaunchKernelGGL(k_pick_u64, dim3(grid_each(res->T)), dim3(256), 0, st, ks, res->first, res->T, g.as<u64>());
         KERNEL_CHECK();
         HIP_TRY(hipMemcpyAsync(res->first, g.p, (size_t)res->T * 8, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));

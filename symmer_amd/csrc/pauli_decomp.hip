@@ -34,22 +34,6 @@ constexpr u32 PD_BAD_INDEX = 1u, PD_BAD_INDPTR = 2u;
 
 struct PdXBlock { u32 x0, first_rank, mask; u32 pad; };   // an aligned block of 32 x values: which are listed, and the rank of the first
 
-static int pd_grid(i64 n, int block = 256) {
-    i64 g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : g);
-}
-
-// first position in the ascending v[0..n) holding a value >= key
-template <typename T>
-__device__ __forceinline__ i64 pd_lower_bound(const T *v, i64 n, u64 key) {
-    i64 lo = 0, hi = n;
-    while (lo < hi) {
-        const i64 mid = (lo + hi) >> 1;
-        if ((u64)v[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // ---- 2. gather ---------------------------------------------------------------------------------------------------------------------
 // grid (b-blocks, x-blocks); tile[r][c] = M[b0 + r][(b0 ^ x0) + c]; scratch[rank(x0 + xj)][b0 + r] = tile[r][r ^ xj].  The transposed
 // read is conflict-free: a row of the tile is 512 B = two bank rows, and the 16 lanes of a ds_read_b128 group hold 16 distinct r mod 16.
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(256) void k_pd_heads(const u64 *__restrict__ key, i
     if (s >= T) return;
     bool h = s == 0 || key[s] != key[s - 1];
     if (h && basis_xs) {
-        const i64 p = pd_lower_bound(basis_xs, Db, key[s]);
+        const i64 p = lower_bound(basis_xs, Db, key[s]);
         h = p < Db && basis_xs[p] == key[s];
     }
     head[s] = h ? 1u : 0u;
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(256) void k_pd_scatter(const f64x2 *__restrict__ da
     const u64 N = (u64)1 << n;
     const u64 row = row_of[e];
     const u64 key = (row ^ (u64)indices[e]) & (N - 1);
-    const i64 j = pd_lower_bound(xs, D, key);
+    const i64 j = lower_bound(xs, D, key);
     if (j < D && xs[j] == key) scratch[(size_t)j * N + row] = data[e];
 }
 
@@ -292,7 +276,7 @@ __global__ __launch_bounds__(256) void k_pd_pick(PdSlots P, i64 D, const u64 *__
     const i64 k = (i64)blockIdx.x * 256 + threadIdx.x;
     if (k >= K) return;
     const u64 x = bx[k], z = bz[k];
-    const i64 j = P.xs ? pd_lower_bound(P.xs, D, x) : (i64)x;
+    const i64 j = P.xs ? lower_bound(P.xs, D, x) : (i64)x;
     f64x2 c = {0.0, 0.0};
     if (j < D && (!P.xs || P.xs[j] == x)) c = pd_coefficient(P.scratch[((u64)j << P.n) + z], x, z, P.scale);
     out[k] = c;
@@ -431,7 +415,7 @@ static int pd_select_all(const PdPlan &p, const f64x2 *scratch, const u64 *xs, s
 static int pd_select_basis(const PdPlan &p, const f64x2 *scratch, const u64 *xs, const u64 *bx_dev, const u64 *bz_dev, i64 K, double *coeff_out) {
     Scratch picked;
     SG_TRY(picked.alloc((size_t)K * 16));
-    hipLaunchKernelGGL(k_pd_pick, dim3(pd_grid(K)), dim3(256), 0, ctx().stream, pd_slots(p, scratch, xs), (i64)p.D, bx_dev, bz_dev, K, picked.as<f64x2>());
+    hipLaunchKernelGGL(k_pd_pick, dim3(grid_each(K)), dim3(256), 0, ctx().stream, pd_slots(p, scratch, xs), (i64)p.D, bx_dev, bz_dev, K, picked.as<f64x2>());
     KERNEL_CHECK();
     SG_TRY(download_any(picked.p, coeff_out, (size_t)K * 16));
     count_d2h((size_t)K * 16);
@@ -517,7 +501,7 @@ static int pd_csr(const double *data, const IDX *indices, const IDX *indptr, i64
     SG_TRY(flags.alloc(8));
     HIP_TRY(hipMemsetAsync(flags.p, 0, 8, st));
     u32 *d_D = flags.as<u32>() + 1;
-    hipLaunchKernelGGL(k_pd_csr_check_indptr<IDX>, dim3(pd_grid((i64)N + 1)), dim3(256), 0, st, d_ptr.as<IDX>(), nnz, n, flags.as<u32>());
+    hipLaunchKernelGGL(k_pd_csr_check_indptr<IDX>, dim3(grid_each((i64)N + 1)), dim3(256), 0, st, d_ptr.as<IDX>(), nnz, n, flags.as<u32>());
     KERNEL_CHECK();
     u32 w[2] = {0, 0};
     if (nnz > 0) {
@@ -529,7 +513,7 @@ static int pd_csr(const double *data, const IDX *indices, const IDX *indptr, i64
         SG_TRY(row_of.alloc((size_t)nnz * 4));
         SG_TRY(head.alloc((size_t)nnz * 4));
         SG_TRY(excl.alloc((size_t)nnz * 4));
-        hipLaunchKernelGGL(k_pd_csr_keys<IDX>, dim3(pd_grid(nnz)), dim3(256), 0, st, d_idx.as<IDX>(), d_ptr.as<IDX>(), nnz, n, key.as<u64>(),
+        hipLaunchKernelGGL(k_pd_csr_keys<IDX>, dim3(grid_each(nnz)), dim3(256), 0, st, d_idx.as<IDX>(), d_ptr.as<IDX>(), nnz, n, key.as<u64>(),
                            row_of.as<u32>(), flags.as<u32>());
         KERNEL_CHECK();
         SortResult by_x;
@@ -539,14 +523,14 @@ static int pd_csr(const double *data, const IDX *indices, const IDX *indptr, i64
             SG_TRY(bxs.alloc(basis.xs.size() * 8));
             HIP_TRY(hipMemcpyAsync(bxs.p, basis.xs.data(), basis.xs.size() * 8, hipMemcpyHostToDevice, st));
         }
-        hipLaunchKernelGGL(k_pd_heads, dim3(pd_grid(nnz)), dim3(256), 0, st, sorted, nnz, basis.K > 0 ? bxs.as<u64>() : (const u64 *)nullptr,
+        hipLaunchKernelGGL(k_pd_heads, dim3(grid_each(nnz)), dim3(256), 0, st, sorted, nnz, basis.K > 0 ? bxs.as<u64>() : (const u64 *)nullptr,
                            (i64)basis.xs.size(), head.as<u32>());
         KERNEL_CHECK();
         SG_TRY(exclusive_scan_u32(head.as<u32>(), excl.as<u32>(), nnz, d_D));
         SG_TRY(read_back_words(flags.as<u32>(), 2, nullptr, 0, w));
         if (w[0]) { set_error("invalid argument: from_matrix_csr: a column index lies outside [0, 2^n)"); return SYMGPU_E_INVALID; }
         SG_TRY(xs.alloc((size_t)w[1] * 8));
-        hipLaunchKernelGGL(k_pd_compact_xs, dim3(pd_grid(nnz)), dim3(256), 0, st, sorted, head.as<u32>(), excl.as<u32>(), nnz, xs.as<u64>());
+        hipLaunchKernelGGL(k_pd_compact_xs, dim3(grid_each(nnz)), dim3(256), 0, st, sorted, head.as<u32>(), excl.as<u32>(), nnz, xs.as<u64>());
         KERNEL_CHECK();
     } else {
         SG_TRY(read_back_words(flags.as<u32>(), 1, nullptr, 0, w));
@@ -565,7 +549,7 @@ static int pd_csr(const double *data, const IDX *indices, const IDX *indptr, i64
     SG_TRY(scratch.alloc((size_t)p.total * 16));
     if (p.total > 0) {
         HIP_TRY(hipMemsetAsync(scratch.p, 0, (size_t)p.total * 16, st));
-        hipLaunchKernelGGL(k_pd_scatter<IDX>, dim3(pd_grid(nnz)), dim3(256), 0, st, d_data.as<f64x2>(), d_idx.as<IDX>(), row_of.as<u32>(), nnz, n,
+        hipLaunchKernelGGL(k_pd_scatter<IDX>, dim3(grid_each(nnz)), dim3(256), 0, st, d_data.as<f64x2>(), d_idx.as<IDX>(), row_of.as<u32>(), nnz, n,
                            xs.as<u64>(), (i64)D, scratch.as<f64x2>());
         KERNEL_CHECK();
     }

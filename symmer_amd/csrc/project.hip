@@ -17,13 +17,6 @@
 
 namespace symgpu {
 
-static int grid_of(i64 n, int block = 256, int cap = 65535) {
-    i64 g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 // ---- projection ---------------------------------------------------------------------------------------------------------------
 // survive[t] = term t commutes with every stabiliser row; sign[t] = parity of the term's bits under neg_mask (the symplectic positions
 // of the stabilisers whose eigenvalue is -1): the reference's product of eigenvalues over the occupied stabilised positions
@@ -133,24 +126,6 @@ __global__ __launch_bounds__(256) void k_join_probe(const u64 *__restrict__ ra, 
     }
     reinterpret_cast<f64x2 *>(prod)[i] = out;
 }
-// 0 + v[0] + v[1] + ... in that order (the reference's `inner_product += ...` loop): one wavefront, 64 values per step through LDS
-__global__ __launch_bounds__(64) void k_seq_sum(const double *__restrict__ v, i64 N, double *__restrict__ out) {
-    __shared__ f64x2 s_p[2][64];
-    const int lane = threadIdx.x;
-    double re = 0.0, im = 0.0;
-    int buf = 0;
-    for (i64 base = 0; base < N; base += 64, buf ^= 1) {
-        if (base + lane < N) s_p[buf][lane] = reinterpret_cast<const f64x2 *>(v)[base + lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane == 0) {
-            const int m = (int)(N - base < 64 ? N - base : 64);
-            for (int k = 0; k < m; ++k) { const f64x2 p = s_p[buf][k]; re = __dadd_rn(re, p.x); im = __dadd_rn(im, p.y); }
-        }
-    }
-    if (lane == 0) { out[0] = re; out[1] = im; }
-}
 
 }  // namespace symgpu
 
@@ -193,7 +168,7 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
     if (k > 0) HIP_TRY(hipMemcpyAsync(d_stab.p, stab_rows, (size_t)k * W * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_neg.p, neg_mask, (size_t)W * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_src.p, src.data(), src.size() * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_proj_flags, dim3(grid_of(T, 256, 1 << 30)), dim3(256), 0, st, op->rows, T, Wq, d_stab.as<u64>(), k, d_neg.as<u64>(), survive.as<u32>(),
+    hipLaunchKernelGGL(k_proj_flags, dim3(grid_each(T)), dim3(256), 0, st, op->rows, T, Wq, d_stab.as<u64>(), k, d_neg.as<u64>(), survive.as<u32>(),
                        sign.as<unsigned char>());
     KERNEL_CHECK();
     SG_TRY(exclusive_scan_u32(survive.as<u32>(), pos.as<u32>(), T, total.as<u32>()));
@@ -208,7 +183,7 @@ int symgpu_project_dev(symgpu_op_t op, const uint64_t *stab_rows, int k, const u
     }
     SG_TRY(t_rows.alloc((size_t)n_s * W_out * 8));
     SG_TRY(t_coeff.alloc((size_t)n_s * 16));
-    hipLaunchKernelGGL(k_proj_emit, dim3(grid_of(T * W_out, 256, 1 << 30)), dim3(256), 0, st, op->rows, op->coeff, T, Wq, survive.as<u32>(), pos.as<u32>(),
+    hipLaunchKernelGGL(k_proj_emit, dim3(grid_each(T * W_out)), dim3(256), 0, st, op->rows, op->coeff, T, Wq, survive.as<u32>(), pos.as<u32>(),
                        sign.as<unsigned char>(), d_src.as<u32>(), W_out, t_rows.as<u64>(), t_coeff.as<double>());
     KERNEL_CHECK();
     // equal projected terms merge (the reference's .cleanup() at projection/base.py:82)
@@ -242,7 +217,7 @@ int symgpu_noncontextual_dev(symgpu_op_t op, int *is_noncontextual) {
     if (n_nu == 0) return SYMGPU_OK;                                 // everything commutes with everything
     SG_TRY(c_rows.alloc((size_t)n_nu * W2 * 8));
     SG_TRY(c_coeff.alloc((size_t)n_nu * 16));
-    hipLaunchKernelGGL(k_characters, dim3(grid_of(T * W2, 256, 1 << 30)), dim3(256), 0, st, bits.as<u64>(), T, Mw, mask.as<u64>(), flag.as<u32>(), pos.as<u32>(), W2,
+    hipLaunchKernelGGL(k_characters, dim3(grid_each(T * W2)), dim3(256), 0, st, bits.as<u64>(), T, Mw, mask.as<u64>(), flag.as<u32>(), pos.as<u32>(), W2,
                        c_rows.as<u64>(), c_coeff.as<double>());
     KERNEL_CHECK();
     // np.unique(axis=0) of utils.py:587 = the device cleanup of the bit-packed rows (no threshold); the unique characters partition the
@@ -279,11 +254,11 @@ int symgpu_state_inner_dev(symgpu_op_t a, symgpu_op_t b, double *out) {
     SG_TRY(hash_rows(a->rows, Na, W, ha.as<u64>()));
     SG_TRY(hash_rows(b->rows, Nb, W, hb.as<u64>()));
     HIP_TRY(hipMemsetAsync(table.p, 0, cap * 8, st));
-    hipLaunchKernelGGL(k_join_insert, dim3(grid_of(Nb, 256, 1 << 30)), dim3(256), 0, st, hb.as<u64>(), Nb, table.as<u64>(), (u32)(cap - 1));
-    hipLaunchKernelGGL(k_join_probe, dim3(grid_of(Na, 256, 1 << 30)), dim3(256), 0, st, a->rows, a->coeff, ha.as<u64>(), Na, b->rows, b->coeff, hb.as<u64>(), W,
+    hipLaunchKernelGGL(k_join_insert, dim3(grid_each(Nb)), dim3(256), 0, st, hb.as<u64>(), Nb, table.as<u64>(), (u32)(cap - 1));
+    hipLaunchKernelGGL(k_join_probe, dim3(grid_each(Na)), dim3(256), 0, st, a->rows, a->coeff, ha.as<u64>(), Na, b->rows, b->coeff, hb.as<u64>(), W,
                        table.as<u64>(), (u32)(cap - 1), prod.as<double>());
-    hipLaunchKernelGGL(k_seq_sum, dim3(1), dim3(64), 0, st, prod.as<double>(), Na, res.as<double>());
     KERNEL_CHECK();
+    SG_TRY(ordered_sum_dev(prod.as<f64x2>(), Na, res.as<f64x2>()));   // the reference's `inner_product += ...` loop: the left state's order
     u32 w[4] = {0, 0, 0, 0};
     SG_TRY(read_back_words(res.as<u32>(), 4, nullptr, 0, w));
     memcpy(out, w, 16);

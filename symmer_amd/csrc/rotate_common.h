@@ -63,13 +63,6 @@ template <int DEFAULT, int W0, int... WS, class F> inline decltype(auto) wq_disp
     return wq_dispatch<DEFAULT, WS...>(w, static_cast<F &&>(f));
 }
 
-static int grid_for(i64 n, int block = 256, int cap = 8192) {
-    i64 g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 // lanes per row of the word kernels (k_rot_analyze, the chain kernels): the power of two >= Wq, at most 64
 static inline int row_lanes(int Wq) {
     int G = 1;

@@ -1,4 +1,4 @@
-// scan.hip — device-wide exclusive scan (u32) in two forms, and the one-launch population-count scan of a small bitmap.
+// scan.hip — device-wide exclusive scan (u32) in two forms, the one-launch population-count scan of a small bitmap, and the ordered sum.
 #include "sort.h"
 #include "block_scan.h"
 #include <stdlib.h>
@@ -184,6 +184,34 @@ int exclusive_scan_u32(const u32 *in, u32 *out, i64 n, u32 *total_dev) {
         hipLaunchKernelGGL(k_store_total, dim3(1), dim3(1), 0, st, last.as<u32>(), out + (n - 1), total_dev);
         KERNEL_CHECK();
     }
+    return SYMGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ordered sum: 0 + v[0] + v[1] + ... in that order (the reference's `inner_product += ...` loops): one wavefront, 64 values per step
+// through LDS, lane 0 adds
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_ordered_sum(const f64x2 *__restrict__ v, i64 N, f64x2 *__restrict__ out) {
+    __shared__ f64x2 s_p[2][64];
+    const int lane = threadIdx.x;
+    double re = 0.0, im = 0.0;
+    int buf = 0;
+    for (i64 base = 0; base < N; base += 64, buf ^= 1) {
+        if (base + lane < N) s_p[buf][lane] = v[base + lane];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (lane == 0) {
+            const int m = (int)(N - base < 64 ? N - base : 64);
+            for (int k = 0; k < m; ++k) { const f64x2 p = s_p[buf][k]; re = __dadd_rn(re, p.x); im = __dadd_rn(im, p.y); }
+        }
+    }
+    if (lane == 0) *out = f64x2{re, im};
+}
+
+int ordered_sum_dev(const f64x2 *v, i64 N, f64x2 *out) {
+    hipLaunchKernelGGL(k_ordered_sum, dim3(1), dim3(64), 0, ctx().stream, v, N, out);
+    KERNEL_CHECK();
     return SYMGPU_OK;
 }
 

@@ -2,10 +2,10 @@
 //
 // Entry (b, b ^ x_k) += c_k (-i)^{Y_k} (-1)^{|b & z_k|}, qubit 0 the MOST significant bit of b, terms added in operator order; entries
 // whose two components are both +-0 are not stored (NaN and inf are).  Plan:
-//   1. group the terms by X-part: key = bit-reversed x word, stable radix sort of (key, term index); per sorted term its z (reversed),
-//      c' = c (-i)^Y (an exact component swap) and its group word; per group its x and, per bit level l, the size of the sibling
-//      subtree of the binary trie of the sorted x values (sib[d][l]).  Row b lists its groups in the order of x_d ^ b, and the rank of
-//      group d in that order is the sum of sib[d][l] over the levels where x_d ^ b has a one bit.
+//   1. group the terms by X-part (xgroups.h): per sorted term its z, c' = c (-i)^Y and its flagged group word, per group its x; then,
+//      per group and bit level l, the size of the sibling subtree of the binary trie of the sorted x values (sib[d][l]).  Row b lists
+//      its groups in the order of x_d ^ b, and the rank of group d in that order is the sum of sib[d][l] over the levels where x_d ^ b
+//      has a one bit.
 //   2. count pass: one thread per row, the sorted terms staged in LDS a tile at a time (every lane reads the same word: a broadcast),
 //      fp64 adds with the sign taken from the parity of b & z; counts[b] = kept entries of row b (4 B per row).
 //   3. 64-bit exclusive scan of the counts -> indptr (device).
@@ -13,11 +13,11 @@
 //      RB * D slots do not fit, or SYMGPU_CSR_SCRATCH=1, in several launches once the slots of all rows exceed 512 MiB, or
 //      SYMGPU_CSR_SCRATCH_MIB); the slots, read in [row][rank] order, ARE the CSR order, so one block scan per 256 slots compacts them
 //      into coalesced writes of data / indices.
-#include "common.h"
-#include "sort.h"
+#include "xgroups.h"
 #include "block_scan.h"
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 
 namespace symgpu {
 
@@ -27,64 +27,8 @@ constexpr int CSR_SLOT_BYTES = 20;                // value (16 B) + column (4 B)
 constexpr size_t CSR_SLOT_LDS = 72 * 1024;        // slot array of the LDS path: two workgroups per CU (160 KiB)
 constexpr int CSR_MIN_LDS_ROWS = 32;              // fewer rows per workgroup leave too many lanes idle: the scratch form is used
 constexpr size_t CSR_SCRATCH_MAX = (size_t)512 << 20;   // global slot scratch per launch of the fallback (raised to 4 workgroups per CU)
-constexpr u32 CSR_FIRST = 1u << 31, CSR_LAST = 1u << 30, CSR_GID = CSR_LAST - 1;
 constexpr int CSR_SCAN_ITEMS = 4096;              // counts per workgroup of the 64-bit scan
 constexpr u64 CSR_MAX_GRID = (u64)1 << 22;       // workgroups per fill launch
-
-static int csr_grid(i64 n, int block = 256) {
-    i64 g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : g);
-}
-
-// ---- 1. grouping -------------------------------------------------------------------------------------------------------------
-// (matvec.hip restates k_csr_keys, k_csr_heads and the sort / scan sequence of csr_count for its plan: keep the two in step)
-__global__ __launch_bounds__(256) void k_csr_keys(const u64 *__restrict__ rows, i64 T, int n, u64 *__restrict__ key, u32 *__restrict__ idx) {
-    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (t >= T) return;
-    key[t] = __brevll(rows[2 * t]) >> (64 - n);
-    idx[t] = (u32)t;
-}
-
-__global__ __launch_bounds__(256) void k_csr_heads(const u64 *__restrict__ key, i64 T, u32 *__restrict__ head) {
-    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= T) return;
-    head[s] = (s == 0 || key[s] != key[s - 1]) ? 1u : 0u;
-}
-
-// c' = c (-i)^Y: exact (a swap and sign flips, no arithmetic)
-__device__ __forceinline__ f64x2 times_minus_i_pow(f64x2 c, int y) {
-    switch (y & 3) {
-        case 0: return c;
-        case 1: return f64x2{c.y, -c.x};
-        case 2: return f64x2{-c.x, -c.y};
-        default: return f64x2{-c.y, c.x};
-    }
-}
-
-__global__ __launch_bounds__(256) void k_csr_terms(const u64 *__restrict__ rows, const double *__restrict__ coeff, const u64 *__restrict__ key,
-                                                   const u32 *__restrict__ idx, const u32 *__restrict__ gexcl, const u32 *__restrict__ head, i64 T, int n,
-                                                   u32 *__restrict__ tz, f64x2 *__restrict__ tc, u32 *__restrict__ tg, u32 *__restrict__ gx) {
-    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= T) return;
-    const u32 t = idx[s];
-    const u64 x = rows[2 * (i64)t], z = rows[2 * (i64)t + 1];
-    const u32 g = gexcl[s] + head[s] - 1;
-    const bool last = s == T - 1 || key[s + 1] != key[s];
-    tz[s] = (u32)(__brevll(z) >> (64 - n));
-    tc[s] = times_minus_i_pow(reinterpret_cast<const f64x2 *>(coeff)[t], __popcll(x & z));
-    tg[s] = g | (head[s] ? CSR_FIRST : 0u) | (last ? CSR_LAST : 0u);
-    if (head[s]) gx[g] = (u32)key[s];
-}
-
-// first position in the ascending gx[0..D) holding a value >= v
-__device__ __forceinline__ u32 csr_lower_bound(const u32 *gx, u32 D, u64 v) {
-    u32 lo = 0, hi = D;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if ((u64)gx[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // sib[d * n + l] = groups that agree with x_d above bit l and differ from it at bit l
 __global__ __launch_bounds__(256) void k_csr_sib(const u32 *__restrict__ gx, u32 D, int n, u32 *__restrict__ sib) {
@@ -94,7 +38,7 @@ __global__ __launch_bounds__(256) void k_csr_sib(const u32 *__restrict__ gx, u32
     const int l = (int)(i - (i64)d * n);
     const u64 x = gx[d];
     const u64 lo = (((x >> (l + 1)) << 1) | (((x >> l) & 1) ^ 1)) << l;
-    sib[i] = csr_lower_bound(gx, D, lo + ((u64)1 << l)) - csr_lower_bound(gx, D, lo);
+    sib[i] = lower_bound(gx, D, lo + ((u64)1 << l)) - lower_bound(gx, D, lo);
 }
 
 // ---- 2 / 4. the row sums -----------------------------------------------------------------------------------------------------
@@ -299,78 +243,44 @@ static size_t csr_scratch_max() {
 
 using namespace symgpu;
 
-// the state a count call leaves for its fill call: the grouped terms and the 64-bit indptr, on the operator's device
+// the state a count call leaves for its fill call: the grouped terms, the trie sizes and the 64-bit indptr, on the operator's device
 struct symgpu_csr_s {
     int device = 0;
-    int n = 0;
-    i64 T = 0;
-    u32 D = 0;
+    XGroups xg;
     u64 nnz = 0;
-    void *tz = nullptr, *tc = nullptr, *tg = nullptr, *gx = nullptr, *sib = nullptr, *indptr = nullptr;
+    Scratch sib, indptr;
 };
 
-static void csr_release(symgpu_csr_s *p) {
-    for (void *q : {p->tz, p->tc, p->tg, p->gx, p->sib, p->indptr})
-        if (q) dev_free(q);
-    delete p;
-}
-
 static CsrTerms csr_terms_of(const symgpu_csr_s *p) {
-    return CsrTerms{(const u32 *)p->tz, (const f64x2 *)p->tc, (const u32 *)p->tg, (const u32 *)p->gx, (const u32 *)p->sib, p->T, p->D, p->n};
+    const XGroups &g = p->xg;
+    return CsrTerms{g.tz.as<u32>(), g.tc.as<f64x2>(), g.tg.as<u32>(), g.gx.as<u32>(), p->sib.as<u32>(), g.T, g.G, g.n};
 }
 
 static int csr_count(symgpu_op_t op, int n, symgpu_csr_s *p) {
     hipStream_t st = ctx().stream;
-    const i64 T = op->T;
     const u64 N = (u64)1 << n;
-    if (T > 0) {
-        Scratch key, key_tmp, idx, idx_tmp, head, gexcl;
-        SG_TRY(key.alloc((size_t)T * 8));
-        SG_TRY(key_tmp.alloc((size_t)T * 8));
-        SG_TRY(idx.alloc((size_t)T * 4));
-        SG_TRY(idx_tmp.alloc((size_t)T * 4));
-        SG_TRY(head.alloc((size_t)T * 4));
-        SG_TRY(gexcl.alloc((size_t)T * 4 + 4));
-        hipLaunchKernelGGL(k_csr_keys, dim3(csr_grid(T)), dim3(256), 0, st, op->rows, T, n, key.as<u64>(), idx.as<u32>());
-        KERNEL_CHECK();
-        SortResult by_x;
-        SG_TRY(radix_sort({key.as<u64>(), key_tmp.as<u64>(), idx.as<u32>(), idx_tmp.as<u32>(), T, 0, (n + 7) / 8 * 8, nullptr, SortForm::Launches}, &by_x));
-        const u64 *k = by_x.keys;
-        const u32 *ix = by_x.vals;
-        hipLaunchKernelGGL(k_csr_heads, dim3(csr_grid(T)), dim3(256), 0, st, k, T, head.as<u32>());
-        KERNEL_CHECK();
-        u32 *d_total = gexcl.as<u32>() + T;
-        SG_TRY(exclusive_scan_u32(head.as<u32>(), gexcl.as<u32>(), T, d_total));
-        u32 D = 0;
-        SG_TRY(read_back_words(d_total, 1, nullptr, 0, &D));
-        p->D = D;
-        SG_TRY(dev_alloc((size_t)T * 4, &p->tz));
-        SG_TRY(dev_alloc((size_t)T * 16, &p->tc));
-        SG_TRY(dev_alloc((size_t)T * 4, &p->tg));
-        SG_TRY(dev_alloc((size_t)D * 4, &p->gx));
-        SG_TRY(dev_alloc((size_t)D * n * 4, &p->sib));
-        hipLaunchKernelGGL(k_csr_terms, dim3(csr_grid(T)), dim3(256), 0, st, op->rows, op->coeff, k, ix, gexcl.as<u32>(), head.as<u32>(), T, n,
-                           (u32 *)p->tz, (f64x2 *)p->tc, (u32 *)p->tg, (u32 *)p->gx);
-        hipLaunchKernelGGL(k_csr_sib, dim3(csr_grid((i64)D * n)), dim3(256), 0, st, (const u32 *)p->gx, D, n, (u32 *)p->sib);
-        KERNEL_CHECK();
-    }
-    SG_TRY(dev_alloc((size_t)(N + 1) * 8, &p->indptr));
-    if (T == 0) {
-        HIP_TRY(hipMemsetAsync(p->indptr, 0, (size_t)(N + 1) * 8, st));
+    SG_TRY(xgroups_build(op, n, true, &p->xg));
+    SG_TRY(p->indptr.alloc((size_t)(N + 1) * 8));
+    if (p->xg.T == 0) {
+        HIP_TRY(hipMemsetAsync(p->indptr.p, 0, (size_t)(N + 1) * 8, st));
         p->nnz = 0;
         return SYMGPU_OK;
     }
+    const u32 D = p->xg.G;
+    SG_TRY(p->sib.alloc((size_t)D * n * 4));
+    hipLaunchKernelGGL(k_csr_sib, dim3(grid_each((i64)D * n)), dim3(256), 0, st, p->xg.gx.as<u32>(), D, n, p->sib.as<u32>());
+    KERNEL_CHECK();
     Scratch counts, sums;
     const u64 nb = (N + CSR_SCAN_ITEMS - 1) / CSR_SCAN_ITEMS;
     SG_TRY(counts.alloc((size_t)N * 4));
     SG_TRY(sums.alloc((size_t)(nb + 1) * 8));
-    hipLaunchKernelGGL(k_csr_count, dim3((unsigned)((N + CSR_WG - 1) / CSR_WG)), dim3(CSR_WG), 0, st, csr_terms_of(p), counts.as<u32>());
+    hipLaunchKernelGGL(k_csr_count, dim3(grid_each((i64)N, CSR_WG)), dim3(CSR_WG), 0, st, csr_terms_of(p), counts.as<u32>());
     hipLaunchKernelGGL(k_csr_scan_sums, dim3((unsigned)nb), dim3(CSR_WG), 0, st, counts.as<u32>(), N, sums.as<u64>());
     hipLaunchKernelGGL(k_csr_scan_top, dim3(1), dim3(CSR_WG), 0, st, sums.as<u64>(), nb);
-    hipLaunchKernelGGL(k_csr_scan_apply, dim3((unsigned)nb), dim3(CSR_WG), 0, st, counts.as<u32>(), N, sums.as<u64>(), nb, (u64 *)p->indptr);
+    hipLaunchKernelGGL(k_csr_scan_apply, dim3((unsigned)nb), dim3(CSR_WG), 0, st, counts.as<u32>(), N, sums.as<u64>(), nb, p->indptr.as<u64>());
     KERNEL_CHECK();
     u32 w[2] = {0, 0};
-    SG_TRY(read_back_words(reinterpret_cast<const u32 *>((const u64 *)p->indptr + N), 2, nullptr, 0, w));
+    SG_TRY(read_back_words(reinterpret_cast<const u32 *>(p->indptr.as<u64>() + N), 2, nullptr, 0, w));
     p->nnz = (u64)w[0] | ((u64)w[1] << 32);
     return SYMGPU_OK;
 }
@@ -394,8 +304,8 @@ static CsrFillForm csr_fill_form(const symgpu_csr_s *p) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_csr_fill<false, int32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CSR_SLOT_LDS) == hipSuccess &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_csr_fill<false, int64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CSR_SLOT_LDS) == hipSuccess);
     if (!lds_attr) note_degraded("to_sparse_matrix fill (k_csr_fill) in LDS off: the runtime refused its LDS size; every fill takes the global-scratch form");
-    const u64 N = (u64)1 << p->n;
-    const size_t per_row = (size_t)p->D * CSR_SLOT_BYTES;
+    const u64 N = (u64)1 << p->xg.n;
+    const size_t per_row = (size_t)p->xg.G * CSR_SLOT_BYTES;
     CsrFillForm f;
     if (lds_attr && per_row * csr_min_lds_rows() <= CSR_SLOT_LDS && !csr_force_scratch()) {
         f.lds = true;
@@ -417,16 +327,16 @@ template <typename IDX>
 static int csr_fill_launch(const symgpu_csr_s *p, const CsrFillForm &f, f64x2 *data, IDX *indices) {
     hipStream_t st = ctx().stream;
     const CsrTerms P = csr_terms_of(p);
-    const size_t per_row = (size_t)p->D * CSR_SLOT_BYTES;
+    const size_t per_row = (size_t)p->xg.G * CSR_SLOT_BYTES;
     Scratch slots;
     if (!f.lds) SG_TRY(slots.alloc(f.scratch_bytes));
     for (u64 b0 = 0; b0 < f.nblk; b0 += f.chunk) {
         const u64 nb = f.nblk - b0 < f.chunk ? f.nblk - b0 : f.chunk;
         if (f.lds)
             hipLaunchKernelGGL((k_csr_fill<false, IDX>), dim3((unsigned)nb), dim3(CSR_WG), (size_t)f.RB * per_row, st, P, f.RB, b0,
-                               (const u64 *)p->indptr, p->nnz, (char *)nullptr, data, indices);
+                               p->indptr.as<u64>(), p->nnz, (char *)nullptr, data, indices);
         else
-            hipLaunchKernelGGL((k_csr_fill<true, IDX>), dim3((unsigned)nb), dim3(CSR_WG), 0, st, P, f.RB, b0, (const u64 *)p->indptr, p->nnz,
+            hipLaunchKernelGGL((k_csr_fill<true, IDX>), dim3((unsigned)nb), dim3(CSR_WG), 0, st, P, f.RB, b0, p->indptr.as<u64>(), p->nnz,
                                slots.as<char>(), data, indices);
         KERNEL_CHECK();
         bump_counter(f.lds ? SYMGPU_CTR_CSR_FILL_LDS : SYMGPU_CTR_CSR_FILL_SCRATCH);   // launches of the fill by form, here and nowhere else
@@ -436,7 +346,7 @@ static int csr_fill_launch(const symgpu_csr_s *p, const CsrFillForm &f, f64x2 *d
 
 static int csr_fill(const symgpu_csr_s *p, double *data, void *indices, void *indptr, int index_bytes) {
     hipStream_t st = ctx().stream;
-    const u64 N = (u64)1 << p->n, nnz = p->nnz;
+    const u64 N = (u64)1 << p->xg.n, nnz = p->nnz;
     if (nnz > 0) {
         Scratch d_data, d_idx;
         SG_TRY(d_data.alloc((size_t)nnz * 16));
@@ -450,11 +360,11 @@ static int csr_fill(const symgpu_csr_s *p, double *data, void *indices, void *in
     if (index_bytes == 4) {
         Scratch ip32;
         SG_TRY(ip32.alloc((size_t)(N + 1) * 4));
-        hipLaunchKernelGGL(k_csr_indptr32, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)p->indptr, N + 1, ip32.as<int32_t>());
+        hipLaunchKernelGGL(k_csr_indptr32, dim3(grid_each((i64)N + 1)), dim3(256), 0, st, p->indptr.as<u64>(), N + 1, ip32.as<int32_t>());
         KERNEL_CHECK();
         SG_TRY(symgpu_dev_download(ip32.p, indptr, (size_t)(N + 1) * 4));
     } else {
-        SG_TRY(symgpu_dev_download(p->indptr, indptr, (size_t)(N + 1) * 8));
+        SG_TRY(symgpu_dev_download(p->indptr.p, indptr, (size_t)(N + 1) * 8));
     }
     return SYMGPU_OK;
 }
@@ -468,27 +378,20 @@ int symgpu_to_csr_count(symgpu_op_t op, int n_qubits, int64_t *nnz, int64_t *fil
     SG_REQUIRE(n_qubits >= 1 && n_qubits <= 31 && op->Wq == 1, "to_csr_count: 1 <= n_qubits <= 31");
     SG_REQUIRE(op->coeff || op->T == 0, "to_csr_count: operator has no coefficients");
     SG_REQUIRE(op->T < ((i64)1 << 30), "to_csr_count: T >= 2^30");
-    symgpu_csr_s *p = new symgpu_csr_s();
+    std::unique_ptr<symgpu_csr_s> p(new symgpu_csr_s());
     p->device = op->device;
-    p->n = n_qubits;
-    p->T = op->T;
-    const int rc = csr_count(op, n_qubits, p);
-    if (rc != SYMGPU_OK) {
-        csr_release(p);
-        return rc;
-    }
+    SG_TRY(csr_count(op, n_qubits, p.get()));
     *nnz = (int64_t)p->nnz;
-    *fill_scratch_bytes = p->nnz > 0 ? (int64_t)csr_fill_form(p).scratch_bytes : 0;
-    *plan = p;
+    *fill_scratch_bytes = p->nnz > 0 ? (int64_t)csr_fill_form(p.get()).scratch_bytes : 0;
+    *plan = p.release();
     return SYMGPU_OK;
 }
 
 int symgpu_to_csr_fill(symgpu_csr_t plan, double *data, void *indices, void *indptr, int index_bytes) {
     SG_REQUIRE(plan, "to_csr_fill: null plan");
     // the plan goes whatever happens, after the scope below has ended (dev_free files a block under its owning device: no context needed)
-    struct PlanRelease { symgpu_csr_t p; ~PlanRelease() { csr_release(p); } } release{plan};
-    symgpu_op_s scope_op;                         // the plan's device, entered the way a call with a handle enters it
-    scope_op.device = plan->device;
+    const std::unique_ptr<symgpu_csr_s> release(plan);
+    const symgpu_op_s scope_op = scope_of_device(plan->device);
     SG_ENTER(&scope_op);
     int rc = SYMGPU_OK;
     if (data || indices || indptr) {

@@ -8,7 +8,7 @@ import pytest
 import scipy.sparse
 
 import _sparse_oracle as so
-from symmer_amd import PauliwordOp, QuantumState, kernels
+from symmer_amd import PauliwordOp, QuantumState, kernels, packing
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +42,43 @@ def assert_csr_equal(got, want, exact=True):
         assert np.array_equal(d.view(np.float64), wd.view(np.float64)), 'data not bit-equal'
     else:
         assert np.allclose(d, wd, rtol=0, atol=1e-12)
+
+
+BALANCE = ('DEV_BLOCKS_LIVE', 'DEV_FREE_UNKNOWN')
+
+
+@pytest.fixture(scope='module', autouse=True)
+def plans_and_buffers_are_balanced():
+    """DEV_BLOCKS_LIVE is the same before and after the module's tests (after one warm-up call: the context keeps its sort state)."""
+    rng = np.random.default_rng(0)
+    kernels.to_csr(PauliwordOp(random_symp(rng, 5, 30), dyadic(rng, 30))._device(), 5)
+    before = kernels.counters(BALANCE)
+    yield
+    assert np.array_equal(kernels.counters(BALANCE), before)
+
+
+def test_a_plan_released_without_a_fill_leaves_nothing():
+    """The routes on which to_csr gives a plan up: a fill call of null buffers, and a fill call that is refused."""
+    import ctypes
+    from symmer_amd import _lib
+    lib = _lib.lib()
+    rng = np.random.default_rng(9)
+    n = 5
+    Z0 = np.zeros((1, 2 * n), dtype=bool); Z0[0, n] = True
+    for symp, c, nnz_want in ((np.vstack([Z0, Z0]), np.array([1.0, -1.0]), 0), (random_symp(rng, n, 30), dyadic(rng, 30), None)):
+        with kernels.DeviceOp.upload(packing.pack_rows(symp), c) as op:
+            before = kernels.counters(BALANCE)
+            for refused in (False, True):
+                nnz, scratch, plan = ctypes.c_int64(-1), ctypes.c_int64(-1), ctypes.c_void_p()
+                _lib.check(lib.symgpu_to_csr_count(op.handle, n, ctypes.addressof(nnz), ctypes.addressof(scratch), ctypes.byref(plan)))
+                assert plan.value and (nnz.value == nnz_want if nnz_want is not None else nnz.value > 0)
+                assert kernels.counters(BALANCE)[0] > before[0], 'the plan holds device blocks'
+                if refused:                                    # an index width that is neither 4 nor 8: refused, the plan released all the same
+                    indptr = np.empty((1 << n) + 1, dtype=np.int64)
+                    assert lib.symgpu_to_csr_fill(plan, None, None, _lib.addr(indptr), 3) == _lib.E_INVALID
+                else:
+                    _lib.check(lib.symgpu_to_csr_fill(plan, None, None, None, 4))
+                assert np.array_equal(kernels.counters(BALANCE), before)
 
 
 # ---- the definition --------------------------------------------------------------------------------------------------------------

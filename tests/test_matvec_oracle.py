@@ -7,6 +7,7 @@ import pytest
 
 import _matvec_oracle as mo
 import _sparse_oracle as so
+import test_gpu_xgroups as xg
 from symmer_amd import QuantumState
 
 
@@ -36,6 +37,18 @@ def test_oracle_no_terms_and_diagonal():
     symp[1:, n:] = np.eye(n, dtype=bool)
     c = np.array([n / 2] + [-0.5] * n)                      # sum_q (1 - Z_q) / 2
     assert np.array_equal(mo.diagonal(symp, c), [bin(b).count('1') for b in range(8)])
+
+
+@pytest.mark.parametrize('n', xg.SIZES)
+def test_sparse_oracle_columns_equal_the_matvec_oracle_on_unit_vectors(n):
+    """The CPU twin of tests/test_gpu_xgroups.py: the property holds between the two restatements, on the same operators."""
+    side = 1 << n
+    for name, symp, c in xg.consumer_cases(n):
+        A = xg.dense_of_csr(so.to_csr(symp, c), n)
+        for j in range(side):
+            e = np.zeros(side, dtype=np.complex128)
+            e[j] = 1.0
+            assert np.array_equal(mo.matvec(symp, c, e), A[:, j]), f'{name}: column {j}'
 
 
 # ---- QuantumState.from_array ---------------------------------------------------------------------------------------------------------
