@@ -168,13 +168,22 @@ int symgpu_prof_read(int kernel_class, int64_t *n_launches, double *total_ms);
     X(DEV_BLOCKS_LIVE, 55, "a GAUGE, not a count: device blocks handed out by the allocator and not yet returned to it (operators, their " \
       "caches, scratch, what the contexts keep); never below 0") \
     X(DEV_FREE_UNKNOWN, 56, "blocks returned to the allocator that it did not hold (a double free, a pointer from elsewhere); the call " \
-      "fails with SYMGPU_E_INVALID and nothing is released")
+      "fails with SYMGPU_E_INVALID and nothing is released") \
+    /* 57-60: builds of what a handle caches between calls (symgpu_op_s, csrc/common.h), bumped where the build happens and nowhere else: a
+     * call that finds its cache valid counts nothing.  tests/test_gpu_handle_state.py asserts through them that a cache is hit while the
+     * rows stay and rebuilt once after every change of rows. */ \
+    X(OP_WORD_MAJOR_BUILDS, 57, "word-major copies of an operator's rows built into its handle (op_wordmajor, layout.hip)") \
+    X(OP_BIT_MAJOR_BUILDS, 58, "bit-major copies of an operator's rows built into its handle for the Four-Russians commutation kernel " \
+      "(m4r_bit_major, commute_m4r.hip; a copy built into the call's scratch counts nothing)") \
+    X(OP_YCOUNT_BUILDS, 59, "Y-count arrays built into an operator's handle (op_ycount, layout.hip)") \
+    X(OP_ROW_HASH_BUILDS, 60, "row-hash arrays computed from an operand's rows into its handle (analyze_rows, rotate_analyze.hip; " \
+      "ensure_row_hashes, rotate_resident.hip); hashes a rotation hands on to its result count nothing")
 #define SYMGPU_COUNTER_ENUM_ENTRY(name, id, text) SYMGPU_CTR_##name = id,
-typedef enum symgpu_counter { SYMGPU_COUNTER_LIST(SYMGPU_COUNTER_ENUM_ENTRY) SYMGPU_CTR_COUNT = 57 } symgpu_counter;
+typedef enum symgpu_counter { SYMGPU_COUNTER_LIST(SYMGPU_COUNTER_ENUM_ENTRY) SYMGPU_CTR_COUNT = 61 } symgpu_counter;
 #undef SYMGPU_COUNTER_ENUM_ENTRY
 /* *value = the counter `which` (an id of the list above; SYMGPU_E_INVALID outside it).  Needs no device and no context. */
 int symgpu_debug_counter(int which, int64_t *value);
-/* The name of counter `which` as spelled in the list ("HASH_RESEEDS", ...), NULL outside 0 .. 56: a binder builds its name -> id map from
+/* The name of counter `which` as spelled in the list ("HASH_RESEEDS", ...), NULL outside 0 .. 60: a binder builds its name -> id map from
  * it instead of copying numbers.  Needs no device and no context. */
 const char *symgpu_debug_counter_name(int which);
 /* The radix sort and the two scans that everything else stands on, run directly on device buffers of the caller's (symgpu_dev_alloc /
@@ -266,7 +275,8 @@ int symgpu_dev_popcount_u64(const uint64_t *dev, int64_t n_words, uint64_t *sum)
 int symgpu_mul_allpairs(const uint64_t *inner, const double *ci, int64_t Ni,
                         const uint64_t *outer, const double *co, int64_t No, int Wq, int inner_is_left,
                         uint64_t *out_rows, double *out_coeff);
-/* device-resident slab: outer rows [o_begin, o_end) -> out (capacity >= (o_end-o_begin)*Ni rows) */
+/* device-resident slab: outer rows [o_begin, o_end) -> out (capacity >= (o_end-o_begin)*Ni rows).  out must be a third handle: out == inner
+ * or out == outer is refused with SYMGPU_E_INVALID (the rows would be read out of the buffer being written). */
 int symgpu_mul_allpairs_dev(symgpu_op_t inner, symgpu_op_t outer, int64_t o_begin, int64_t o_end,
                             int inner_is_left, symgpu_op_t out);
 

@@ -119,7 +119,7 @@ int m4r_bit_major(const CommutePlan &pl, const u64 *B, i64 M, int W, symgpu_op_s
     if (build) {
         hipLaunchKernelGGL(k_m4r_bt, dim3((unsigned)((pl.Mw_pad / 8 + 3) / 4), (unsigned)W), dim3(256), 0, ctx().stream, B, M, W, build, pl.Mw_pad);
         KERNEL_CHECK();
-        if (cache) { cache->bt_pad = pl.Mw_pad; cache->bt_T = M; }
+        if (cache) { cache->bt_pad = pl.Mw_pad; cache->bt_T = M; bump_counter(SYMGPU_CTR_OP_BIT_MAJOR_BUILDS); }
     }
     *bt = cache ? cache->bt : scratch.as<u64>();
     return SYMGPU_OK;

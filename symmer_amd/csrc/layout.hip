@@ -62,6 +62,7 @@ int op_ycount(symgpu_op_s *op, const int **out) {
         op->yc_T = -1;
         SG_TRY(dev_alloc((size_t)(op->T > 0 ? op->T : 1) * sizeof(int), (void **)&op->yc));
         SG_TRY(ycount_dev(op->rows, op->T, op->Wq, op->yc));
+        bump_counter(SYMGPU_CTR_OP_YCOUNT_BUILDS);
         op->yc_T = op->T;
     }
     *out = op->yc;
@@ -78,6 +79,7 @@ int op_wordmajor(symgpu_op_s *op, i64 mult, const u64 **out, i64 *pad) {
         const i64 p = (op->T + m - 1) / m * m;
         SG_TRY(dev_alloc((size_t)(p > 0 ? p : m) * 2 * op->Wq * sizeof(u64), (void **)&op->wm));
         SG_TRY(to_wordmajor(op->rows, op->T, 2 * op->Wq, op->wm, p));
+        bump_counter(SYMGPU_CTR_OP_WORD_MAJOR_BUILDS);
         op->wm_pad = p;
         op->wm_T = op->T;
     }

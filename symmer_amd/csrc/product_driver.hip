@@ -139,6 +139,7 @@ int symgpu_mul_allpairs_dev(symgpu_op_t inner, symgpu_op_t outer, int64_t o_begi
                             symgpu_op_t out) {
     SG_ENTER(inner, outer, out);
     SG_REQUIRE(inner && outer && out, "mul_allpairs_dev: null handle");
+    SG_REQUIRE(out != inner && out != outer, "mul_allpairs_dev: out must not be one of the operands");
     SG_REQUIRE(inner->Wq == outer->Wq && out->Wq == inner->Wq, "mul_allpairs_dev: operands must share Wq");
     SG_REQUIRE(0 <= o_begin && o_begin <= o_end && o_end <= outer->T, "mul_allpairs_dev: bad outer range");
     const i64 rows = (o_end - o_begin) * inner->T;

@@ -262,6 +262,7 @@ int analyze_rows(symgpu_op_t in, u64 *q_dev, u32 *anti, uint8_t *ph, const JoinT
         if (in->hash) { dev_free(in->hash); in->hash = nullptr; }
         SG_TRY(dev_alloc((size_t)in->capacity * 8 + 16, (void **)&in->hash));      // cached on the operand: its next rotation skips the hashing
         in->hash_seed = ctx().hash_seed;
+        bump_counter(SYMGPU_CTR_OP_ROW_HASH_BUILDS);
         words(std::true_type{}, std::true_type{}, ctx().hash_tab, in->hash, nullptr, *jt);
     }
     KERNEL_CHECK();

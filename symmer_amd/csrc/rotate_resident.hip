@@ -56,6 +56,7 @@ static int ensure_row_hashes(symgpu_op_t in) {
     if (in->hash) { dev_free(in->hash); in->hash = nullptr; }
     SG_TRY(dev_alloc((size_t)in->capacity * 8 + 16, (void **)&in->hash));
     in->hash_seed = c.hash_seed;
+    bump_counter(SYMGPU_CTR_OP_ROW_HASH_BUILDS);
     return hash_rows(in->rows, in->T, 2 * in->Wq, in->hash);
 }
 

@@ -565,7 +565,7 @@ def refusal_cases():
     keepalive = (buf, idx_bad, idx_neg, keep_bad, keep_ok, parts)
     cases = [
         # context.hip
-        ('debug_counter/which', 'debug_counter', lambda L, o: L.symgpu_debug_counter(57, byref(n64))),
+        ('debug_counter/which', 'debug_counter', lambda L, o: L.symgpu_debug_counter(61, byref(n64))),
         ('current_device/null', 'current_device', lambda L, o: L.symgpu_current_device(None)),
         ('n_initialised/null', 'n_initialised', lambda L, o: L.symgpu_n_initialised(None)),
         # alloc.hip
@@ -668,6 +668,9 @@ def refusal_cases():
         ('mul_allpairs_dev/Wq-mismatch', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.a, I64(0), I64(1), 1, o.w1)),
         ('mul_allpairs_dev/outer-range', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.a, I64(0), I64(13), 1, o.b)),
         ('mul_allpairs_dev/null-out', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.a, I64(0), I64(1), 1, None)),
+        # the rows would be read out of the buffer being written (and the handle's caches are dropped first): refused before anything is touched
+        ('mul_allpairs_dev/out-is-inner', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.a, o.b, I64(0), I64(1), 1, o.a)),
+        ('mul_allpairs_dev/out-is-outer', 'mul_allpairs_dev', lambda L, o: L.symgpu_mul_allpairs_dev(o.b, o.a, I64(0), I64(1), 1, o.a)),
         # gf2_driver.hip
         ('rref/negative-R', 'rref', lambda L, o: L.symgpu_rref(R(o), I64(-1), I64(4), None, None)),
         ('rref/null-rows', 'rref', lambda L, o: L.symgpu_rref(None, I64(12), I64(4), None, None)),

@@ -257,6 +257,188 @@ def test_rotation_results_are_resident_and_chain():
     assert_op_equal(chained.symp_matrix, chained.coeff_vec, es, ec, exact=False, tol=1e-12)
 
 
+# ---------------------------------------------------------------- seeded workflows against a NumPy twin ---------------------------------
+# The drop-in class keeps an operator resident over a whole workflow and refreshes what a host-side write changed.  The existing coherence
+# test observes through `*` alone; here a seeded driver takes a few operators through the class's operations — with coefficient writes in
+# the three reference idioms, a write through an alias held across a device call, copies that share a handle and rotations that return
+# the operator itself in between — and observes through every consumer: rotation, sum, cleanup, expval, commutes_termwise, Y_count, ==.
+# The twin holds NumPy `symp` and `coeff`; every operation on it is oracle_np's.  Dyadic coefficients and Clifford angles: exact; each
+# workflow ends with one true angle, compared within 1e-12.
+import _expval_oracle as eo
+import _handle_model as hm
+
+
+class Twin:
+    def __init__(self, symp, coeff):
+        self.symp, self.coeff = np.asarray(symp, dtype=bool).copy(), np.asarray(coeff, dtype=complex).copy()
+
+    def op(self):
+        return PauliwordOp(self.symp, self.coeff)
+
+
+def workflow_dyadic(rng, t):
+    """k / 16 per component, k != 0: no coefficient is zero, conjugation and every scale show."""
+    pick = lambda: rng.choice(np.concatenate([np.arange(-8, 0), np.arange(1, 9)]), t)
+    return (pick() + 1j * pick()) / 16.0
+
+
+@pytest.mark.parametrize('seed', range(10))
+def test_seeded_workflows_agree_with_a_numpy_twin(seed):
+    from symmer_amd import QuantumState
+    rng = np.random.default_rng([601, seed])
+    n = 70
+    rows = lambda t: rng.random((t, 2 * n)) < 0.3
+    Q = lambda q: PauliwordOp(np.asarray(q, dtype=bool).reshape(1, -1), [1])
+    bits, amps = rng.integers(0, 2, (6, n)), workflow_dyadic(rng, 6)         # six basis states: expval takes the batched device call
+    bits[:, :3] = (np.arange(6)[:, None] >> np.arange(3)) & 1               # ... all different
+    psi = QuantumState(bits, amps)
+    twins = [Twin(rows(t), workflow_dyadic(rng, t)) for t in rng.integers(40, 151, 3)]
+    ops = [t.op() for t in twins]
+    seen = dict.fromkeys(('device_only', 'shared', 'returned_self'), 0)
+
+    def observe(i, where, tol=None):
+        """Everything that reads ops[i]: device-side consumers always, the operator's own arrays every other time (reading them caches them
+        on the host, and the device-only state is part of what is tested)."""
+        A, T = ops[i], twins[i]
+        other = twins[(i + 1) % 3]
+        seen['device_only'] += is_device_only(A)
+        seen['shared'] += A._dev is not None and A._dev.shared
+        assert A.n_terms == T.symp.shape[0], where
+        assert np.array_equal(A.Y_count, onp.y_count(T.symp)), (where, 'Y_count')
+        assert np.array_equal(A.commutes_termwise(ops[(i + 1) % 3]), onp.commutes_termwise(T.symp, other.symp)), (where, 'commutes_termwise')
+        exact = tol is None
+        C = A.cleanup()
+        assert_op_equal(C.symp_matrix, C.coeff_vec, *onp.cleanup_op(T.symp, T.coeff), exact=exact, tol=tol or 0), (where, 'cleanup')
+        want = eo.expval(T.symp, T.coeff, bits, amps)[1]
+        got = A.expval(psi)
+        # (every |<psi|P|psi>| <= <psi|psi>, and a coefficient within tol of the twin's moves the sum by at most tol <psi|psi>)
+        assert got == want if exact else abs(got - want) <= tol * T.coeff.shape[0] * float(np.sum(np.abs(amps) ** 2)), (where, 'expval', got, want)
+        if rng.integers(2):
+            assert np.array_equal(A.symp_matrix, T.symp), (where, 'symp_matrix')
+            assert np.array_equal(A.coeff_vec, T.coeff) if exact else np.allclose(A.coeff_vec, T.coeff, rtol=0, atol=tol), (where, 'coeff_vec')
+            assert A == T.op(), (where, '==')
+
+    def partner(symp):
+        for _ in range(40 if symp.shape[0] > 1 else 0):
+            a, b = rng.choice(symp.shape[0], 2, replace=False)
+            if not onp.commutes_termwise(symp[a:a + 1], symp[b:b + 1])[0, 0]:
+                return symp[a] ^ symp[b]
+        return rows(1)[0]
+
+    def step(i, kind):
+        A, T = ops[i], twins[i]
+        j = (i + int(rng.integers(1, 3))) % 3
+        if kind == 'mul':                                                  # by a few terms, from either side
+            F = Twin(rows(int(rng.integers(2, 5))), workflow_dyadic(rng, 1)[0] * np.ones(1))
+            F.coeff = workflow_dyadic(rng, F.symp.shape[0])
+            left = bool(rng.integers(2))
+            ops[i] = (A * F.op()) if left else (F.op() * A)
+            T.symp, T.coeff = onp.mul(T.symp, T.coeff, F.symp, F.coeff) if left else onp.mul(F.symp, F.coeff, T.symp, T.coeff)
+        elif kind in ('add', 'sub'):
+            sign = 1 if kind == 'add' else -1
+            ops[i] = (A + ops[j]) if kind == 'add' else (A - ops[j])
+            T.symp, T.coeff = onp.symplectic_cleanup(np.vstack([T.symp, twins[j].symp]), np.hstack([T.coeff, sign * twins[j].coeff]), 1e-15)
+        elif kind == 'cleanup':
+            ops[i] = A.cleanup()
+            T.symp, T.coeff = onp.cleanup_op(T.symp, T.coeff)
+        elif kind == 'rotate':
+            q, k = partner(T.symp), int(rng.integers(0, 4))
+            ops[i] = A._rotate_by_single_Pword(Q(q), k * np.pi / 2)
+            T.symp, T.coeff = onp.rotate_by_single_pword(T.symp, T.coeff, q, k * np.pi / 2)
+        elif kind == 'rotate_commuting':                                   # the identity commutes with every term: the rotation returns the operator itself
+            ops[i] = A._rotate_by_single_Pword(Q(np.zeros(2 * n, dtype=bool)), float(rng.choice([0.3, np.pi / 2])))
+            seen['returned_self'] += ops[i] is A
+        elif kind == 'perform_rotations':
+            rots = [(partner(T.symp) if r == 0 else rows(1)[0], int(rng.integers(0, 4)) * np.pi / 2) for r in range(3)]
+            ops[i] = A.perform_rotations([(Q(q), a) for q, a in rots])
+            T.symp, T.coeff = onp.perform_rotations(T.symp, T.coeff, rots)
+        elif kind == 'getitem':
+            t = T.symp.shape[0]
+            which = int(rng.integers(4))
+            if which == 0:
+                key = int(rng.integers(-t, t)); idx = [key]
+            elif which == 1:
+                lo = int(rng.integers(0, t // 2)); key = slice(lo, lo + int(rng.integers(5, t - lo + 1)), int(rng.integers(1, 3))); idx = key
+            elif which == 2:
+                key = [int(v) for v in rng.integers(0, t, int(rng.integers(5, 40)))]; key[1] = key[0]; idx = key        # a repeat
+            else:
+                key = rng.random(t) < 0.6; key[:5] = True; idx = key
+            if which == 0:
+                ops[j], twins[j] = A[key], Twin(T.symp[idx], T.coeff[idx])     # one term: into another slot
+                return j
+            ops[i] = A[key]
+            T.symp, T.coeff = T.symp[idx], T.coeff[idx]
+        elif kind == 'copy':                                               # slot j becomes a copy of slot i: a handle, if there is one, is shared
+            ops[j], twins[j] = A.copy(), Twin(T.symp, T.coeff)
+            return j
+        elif kind == 'dagger':
+            ops[i] = A.dagger
+            T.coeff = T.coeff.conjugate()
+        elif kind == 'constant':
+            const = complex(rng.choice([2.0, -0.5, 0.5j, 1 + 1j, -1j]))
+            ops[i] = A.multiply_by_constant(const) if rng.integers(2) else A * const
+            T.coeff = T.coeff * const
+        elif kind == 'coeff_item':
+            k, x = int(rng.integers(T.coeff.shape[0])), workflow_dyadic(rng, 1)[0]
+            A.coeff_vec[k] = x
+            T.coeff[k] = x
+        elif kind == 'coeff_imul':
+            const = complex(rng.choice([-1.0, 2.0, 0.5, 1j]))
+            A.coeff_vec *= const
+            T.coeff = T.coeff * const
+        elif kind == 'coeff_assign':
+            T.coeff = workflow_dyadic(rng, T.coeff.shape[0])
+            A.coeff_vec = T.coeff.copy()
+        elif kind == 'alias':                                              # an alias held across a device call, then written through
+            held = A.coeff_vec
+            observe(i, (seed, 'alias outstanding'))
+            held *= -2
+            k, x = int(rng.integers(T.coeff.shape[0])), workflow_dyadic(rng, 1)[0]
+            held[k] = x
+            T.coeff = T.coeff * -2
+            T.coeff[k] = x
+        else:
+            raise KeyError(kind)
+        return i
+
+    KINDS = ['mul', 'add', 'sub', 'cleanup', 'rotate', 'rotate', 'rotate_commuting', 'perform_rotations', 'getitem', 'copy', 'copy', 'dagger', 'constant',
+             'coeff_item', 'coeff_imul', 'coeff_assign', 'alias']
+    WRITES = ['coeff_item', 'coeff_imul', 'coeff_assign', 'alias']
+    last = None
+    for s in range(28):
+        i = int(rng.integers(3))
+        kind = str(rng.choice(KINDS))
+        if last is not None and last[1] in ('copy', 'rotate_commuting', 'constant', 'mul') and rng.random() < 0.7:
+            i, kind = last[0], str(rng.choice(WRITES))                     # a host-side write right after a copy / a returned self / a device-only result
+        T = twins[i]
+        if T.symp.shape[0] > 400 or (kind in ('mul', 'add', 'sub') and T.symp.shape[0] > 150):
+            kind = 'getitem'                                               # keep the sizes where they are
+        if T.symp.shape[0] < 12:
+            kind = 'add'
+        if hm.span(T.coeff) > 16 or not np.all(T.coeff != 0):
+            kind = 'coeff_assign'                                          # exact arithmetic: renew coefficients before they outgrow a double
+        touched = step(i, kind)
+        if twins[touched].symp.shape[0] == 0:                              # everything cancelled: start the slot afresh
+            twins[touched] = Twin(rows(60), workflow_dyadic(rng, 60))
+            ops[touched] = twins[touched].op()
+        last = (touched, kind)
+        observe(touched, (seed, s, kind))
+        if kind in ('copy', 'rotate_commuting') or kind in WRITES:         # neither side of a shared handle sees the other's coefficients
+            for o in range(3):
+                if o != touched:
+                    observe(o, (seed, s, kind, 'bystander', o))
+    # one true angle on every operator: within 1e-12, through the rotation and every observer
+    for i in range(3):
+        q = partner(twins[i].symp)
+        ops[i] = ops[i]._rotate_by_single_Pword(Q(q), 0.37)
+        twins[i].symp, twins[i].coeff = onp.rotate_by_single_pword(twins[i].symp, twins[i].coeff, q, 0.37)
+        keep = np.abs(twins[i].coeff) > 1e-9
+        assert keep.all()                                                  # (no ghost row: the comparison below is row for row)
+        observe(i, (seed, 'true angle', i), tol=1e-12)
+    print(seed, seen)
+    assert seen['device_only'] > 0 and seen['shared'] > 0
+
+
 # ---------------------------------------------------------------- single-process multi-device mode (symmer_amd/multi.py), one device ----
 def test_device_group_on_one_device_runs_the_grouped_rccl_path(monkeypatch):
     """The pool has one GPU per box: DeviceGroup over HipBackend(1) with SYMGPU_FORCE_COMM=1 goes through symgpu_init_all, ncclCommInitAll

@@ -365,25 +365,26 @@ COUNTER_IDS = [
     (43, 'GIVEUP_OPERAND_BUCKET'), (44, 'FLOW_SORTED_WHOLE'), (45, 'FLOW_SORTED_FLAGGED'), (46, 'FLOW_MARKED_FROM_BYTES'),
     (47, 'FLOW_FULL_SORT_REPEAT'), (48, 'PRODUCT_ROWS_ONLY'), (49, 'PRODUCT_PHASE_STREAM'), (50, 'PRODUCT_WIDE_COEFF_THEN_ROWS'),
     (51, 'PRODUCT_WORD_MAJOR_THEN_ROWS'), (52, 'PRODUCT_WORD_MAJOR_BESIDE_ROWS'), (53, 'CSR_FILL_LDS'), (54, 'CSR_FILL_SCRATCH'),
-    (55, 'DEV_BLOCKS_LIVE'), (56, 'DEV_FREE_UNKNOWN'),
+    (55, 'DEV_BLOCKS_LIVE'), (56, 'DEV_FREE_UNKNOWN'), (57, 'OP_WORD_MAJOR_BUILDS'), (58, 'OP_BIT_MAJOR_BUILDS'), (59, 'OP_YCOUNT_BUILDS'),
+    (60, 'OP_ROW_HASH_BUILDS'),
 ]
 
 
 def test_debug_counter_ids_and_names_are_frozen():
     """symgpu_debug_counter_name spells exactly the table above (so does the map the Python side builds from it), NULL outside it; every id
-    reads without a device and 57 is the first that does not; an unknown name is a KeyError that names it."""
+    reads without a device and 61 is the first that does not; an unknown name is a KeyError that names it."""
     from symmer_amd import kernels
     lib = _lib.load()
-    assert [i for i, _ in COUNTER_IDS] == list(range(57)) and len({name for _, name in COUNTER_IDS}) == 57
-    got = [(i, lib.symgpu_debug_counter_name(i)) for i in range(57)]
+    assert [i for i, _ in COUNTER_IDS] == list(range(61)) and len({name for _, name in COUNTER_IDS}) == 61
+    got = [(i, lib.symgpu_debug_counter_name(i)) for i in range(61)]
     assert [(i, name.decode('ascii') if name is not None else None) for i, name in got] == COUNTER_IDS
-    assert lib.symgpu_debug_counter_name(-1) is None and lib.symgpu_debug_counter_name(57) is None
+    assert lib.symgpu_debug_counter_name(-1) is None and lib.symgpu_debug_counter_name(61) is None
     assert _lib.counter_ids() == {name: i for i, name in COUNTER_IDS}
     v = ctypes.c_int64(-1)
     for i, name in COUNTER_IDS:
         assert lib.symgpu_debug_counter(i, ctypes.addressof(v)) == _lib.OK and v.value >= 0, name
         assert kernels.counter(name) == v.value
-    assert lib.symgpu_debug_counter(57, ctypes.addressof(v)) == _lib.E_INVALID and lib.symgpu_debug_counter(-1, ctypes.addressof(v)) == _lib.E_INVALID
+    assert lib.symgpu_debug_counter(61, ctypes.addressof(v)) == _lib.E_INVALID and lib.symgpu_debug_counter(-1, ctypes.addressof(v)) == _lib.E_INVALID
     assert kernels.counters(['H2D_BYTES', 'CSR_FILL_SCRATCH']).dtype == np.int64
     with pytest.raises(KeyError, match='no_such'):
         kernels.counter('no_such')
