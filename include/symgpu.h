@@ -471,6 +471,64 @@ int symgpu_lanczos_step(struct symgpu_matvec_s *plan, const uint8_t *keep_dev /*
                         double *alpha, double *beta);
 int symgpu_vec_combine(const double *basis_dev, int64_t m, int n_qubits, const double *s_host, double *out_dev, int normalise);
 
+/* ---- f8: variational states on a dense statevector (symmer/evolution/variational_optimization.py VQE_Driver, ADAPT_VQE; csrc/ansatz.hip):
+ * |psi(theta)> = U_{K-1} ... U_0 |ref>, U_k = exp(i theta_k P_k) = cos theta_k + i sin theta_k P_k, the energy <psi|H|psi>, its gradient
+ * by one reverse sweep, and the gradient of a whole operator pool.  Conventions of f5 / f7: qubit 0 is the MOST significant bit of a basis
+ * index b; for a generator with X part x, Z part z (n-bit integers) and Y = |x & z|:  (P v)[b] = (-i)^Y (-1)^{|b & z|} v[b ^ x].
+ * Vectors are complex128 [2^n] device buffers of symgpu_dev_alloc; n_qubits 1 .. 32, anything else SYMGPU_E_INVALID before anything is
+ * allocated; the rows of gens / pool have Wq = 1, their coefficients are not read.
+ * symgpu_ansatz_plan   takes the K rows of a resident operator in operator order, not cleaned (a repeated generator is its own parameter;
+ *   an identity row is a valid generator, a global phase) and keeps x, z and Y mod 4 of each resident in *plan (16 bytes each); the
+ *   operator is not referenced afterwards.  K = 0 is a valid plan.  symgpu_ansatz_free frees it; symgpu_ansatz_info reports n, K, the
+ *   number of tiled runs (below) and the device bytes (16 K, 32 K when there is a tiled run); any output may be NULL.
+ * symgpu_ansatz_apply   applies U_k for k = k_begin .. k_end-1 to psi_dev in place, in that order, or with reverse != 0 from k_end-1 down
+ *   to k_begin.  cos_t / sin_t: host double [K], indexed by k, the caller's cos theta_k and sin theta_k (the device arithmetic does not
+ *   depend on a libm); pass -sin for the inverse rotations.  Per amplitude, with a = psi[b], p = psi[b ^ x] (p = a for x = 0),
+ *   c = cos_t[k], s' = +-sin_t[k] with the sign (-1)^{|b & z| + (Y >> 1)} (an exact sign change):
+ *     odd Y:   psi'[b] = (c a.re + s' p.re, c a.im + s' p.im)          even Y:   psi'[b] = (c a.re + (-(s' p.im)), c a.im + s' p.re)
+ *   every product and every sum rounded once to IEEE double, nothing contracted: a NumPy restatement gives the same bits.  One launch per
+ *   rotation over the 2^(n-1) SLOTS: slot t owns, for x != 0, the pair (b0, b0 ^ x) where b0 is t with a clear bit inserted at the top set
+ *   bit of x, and for x = 0 the elements t and t + 2^(n-1); its thread reads both and writes both (64-bit indices).
+ *   That is the DIRECT form.  The TILED form gives the same bits with one pass over the vector per RUN of rotations.  The plan cuts the
+ *   sequence greedily: a run's tile bits S start as the 4 lowest index bits (contiguous pieces of 256 bytes) and grow by each generator's
+ *   X-part while |S| <= min(n, 12) (2^12 amplitudes = 64 KiB of LDS); x = 0 joins any open run; a generator that does not fit closes the
+ *   run and opens the next, or, when its own X-part with the 4 low bits exceeds the budget, takes a direct pass; a closed run of fewer
+ *   than min(n, 10) tile bits takes the lowest free bits up to that number.  A workgroup loads the 2^|S| amplitudes that agree outside S,
+ *   applies the run's rotations (those of the requested range) in LDS with a barrier between them — the same arithmetic, the sign of the
+ *   bits outside S uniform to the workgroup — and writes them back.  Runs are planned on the whole sequence; a range clips them.
+ *   *form (may be NULL) = SYMGPU_ANSATZ_DIRECT | SYMGPU_ANSATZ_TILED, the forms that ran; 0 when no rotation ran.
+ *   SYMGPU_ANSATZ_FORM=direct (read on every call) forces direct passes, also in the forward half of symgpu_ansatz_energy_grad; the
+ *   reverse sweep is always direct.
+ * symgpu_ansatz_energy_grad   psi = a copy of ref_dev, all K rotations applied; phi = H psi (symgpu_matvec_apply's kernel and order);
+ *   *energy = Re<psi, phi> in the two-level order of symgpu_lanczos_step (the same kernels).  psi_out_dev (or NULL) gets psi, the bits of
+ *   symgpu_ansatz_apply.  grad_host (double [K] or NULL) gets dE/dtheta_k from one reverse sweep with lambda = phi: for k = K-1 .. 0 one
+ *   launch forms t_k = sum_b Im conj(lambda[b]) (P_k psi)[b] from the values before the update and applies U_k^+ (c, -s) to psi and lambda
+ *   in place (a slot's thread reads four amplitudes and writes four); g_k = -2 t_k.  For a Pauli generator g_k equals the parameter shift
+ *   E(theta + pi/4 e_k) - E(theta - pi/4 e_k).  Order of t_k: the slots are cut into chunks of C = max(256, 2^(n-1) / 1024) consecutive
+ *   slots; thread t of 256 adds (term of b0 + term of b1) of slots t, t + 256, ... of its chunk to 0 in ascending order, a term being
+ *   lambda.re q.im - lambda.im q.re for q = (P_k psi)[b]; the 256 thread sums are folded by halving (s[t] += s[t + 128], then 64, ... 1);
+ *   after the sweep one launch adds the chunk sums of every k to 0 in ascending chunk order and multiplies by -2.  Only K + 1 doubles
+ *   return to the host, in one read-back.  Scratch: two vectors, the [K][chunks] chunk sums when a gradient is asked for.
+ * symgpu_pool_gradient   phi = H psi once; grad_host[j] = -2 sum_b Im conj(phi[b]) (P_j psi)[b] = <psi| i [H, P_j] |psi> for every row j of
+ *   `pool` (on the plan's device); *energy (or NULL) = Re<psi, phi> as above.  Order: the 2^n elements are cut into chunks of
+ *   C = max(256, 2^n / 1024); workgroup (chunk, j): thread t adds the terms of elements t, t + 256, ... of the chunk to 0 in ascending
+ *   order, the thread sums folded by halving; one launch adds the chunk sums in ascending chunk order and multiplies by -2.  M = 0 with
+ *   energy NULL returns at once.  One read-back of M + 1 doubles.
+ * No floating-point atomics anywhere: two calls with the same input give the same bits.  The device memory is checked before it is
+ * allocated (SYMGPU_E_NOMEM); every scratch buffer is freed before a call returns, also on failure. */
+#define SYMGPU_ANSATZ_DIRECT 1
+#define SYMGPU_ANSATZ_TILED 2
+struct symgpu_ansatz_s;   /* a plan: opaque, owned by the caller between symgpu_ansatz_plan and symgpu_ansatz_free */
+int symgpu_ansatz_plan(symgpu_op_t gens, int n_qubits, struct symgpu_ansatz_s **plan);
+int symgpu_ansatz_free(struct symgpu_ansatz_s *plan);
+int symgpu_ansatz_info(struct symgpu_ansatz_s *plan, int *n_qubits, int64_t *n_generators, int64_t *n_runs, int64_t *device_bytes);
+int symgpu_ansatz_apply(struct symgpu_ansatz_s *plan, const double *cos_t, const double *sin_t, int64_t k_begin, int64_t k_end, int reverse,
+                        double *psi_dev, int *form /* or NULL */);
+int symgpu_ansatz_energy_grad(struct symgpu_ansatz_s *plan, struct symgpu_matvec_s *plan_H, const double *cos_t, const double *sin_t,
+                              const double *ref_dev, double *psi_out_dev /* or NULL */, double *energy, double *grad_host /* [K] or NULL */);
+int symgpu_pool_gradient(struct symgpu_matvec_s *plan_H, symgpu_op_t pool, const double *psi_dev, double *energy /* or NULL */,
+                         double *grad_host /* [M] */);
+
 /* ---- f6: PauliwordOp.from_matrix (base.py:239-425), the inverse of f5: the Pauli decomposition of a 2^n x 2^n matrix M, n_qubits 1 .. 31
  * (csrc/pauli_decomp.hip).  With the conventions of f5 (qubit 0 the MOST significant bit of b, x, z):
  *   c(x, z) = i^{|x & z| mod 4} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]

@@ -123,6 +123,12 @@ SIGNATURES = {
     'symgpu_matvec_sector_mask': [P, c_i64, P, P],
     'symgpu_lanczos_step': [P, P, P, c_i64, c_i64, P, P],
     'symgpu_vec_combine': [P, c_i64, c_int, P, P, c_int],
+    'symgpu_ansatz_plan': [P, c_int, PP],
+    'symgpu_ansatz_free': [P],
+    'symgpu_ansatz_info': [P, P, P, P, P],
+    'symgpu_ansatz_apply': [P, P, P, c_i64, c_i64, c_int, P, P],
+    'symgpu_ansatz_energy_grad': [P, P, P, P, P, P, P, P],
+    'symgpu_pool_gradient': [P, P, P, P, P],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

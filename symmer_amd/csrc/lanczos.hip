@@ -16,7 +16,7 @@ namespace symgpu {
 constexpr int LZ_WG = 256;
 
 static u64 lz_chunk(u64 N) { return (N >> 10) > LZ_WG ? (N >> 10) : LZ_WG; }
-static unsigned lz_chunks(u64 N) { return (unsigned)((N + lz_chunk(N) - 1) / lz_chunk(N)); }
+unsigned lz_chunks(u64 N) { return (unsigned)((N + lz_chunk(N) - 1) / lz_chunk(N)); }
 
 // partial[c * nvec + i] = sum over chunk c of conj(basis_i[b]) w[b]; blockIdx.x = chunk, blockIdx.y = i
 __global__ __launch_bounds__(LZ_WG) void k_lz_dots(const f64x2 *basis, u64 N, u64 chunk, int nvec, const f64x2 *w, f64x2 *__restrict__ partial) {
@@ -112,6 +112,16 @@ static int lz_dots(LzWork &k, const f64x2 *basis, u64 N, int nvec, const f64x2 *
     const unsigned chunks = lz_chunks(N);
     hipLaunchKernelGGL(k_lz_dots, dim3(chunks, (unsigned)nvec), dim3(LZ_WG), 0, st, basis, N, lz_chunk(N), nvec, w, k.partial.as<f64x2>());
     hipLaunchKernelGGL(k_lz_reduce, dim3(1), dim3(LZ_WG), 0, st, k.partial.as<f64x2>(), chunks, nvec, k.h.as<f64x2>(), alpha_of, norm, k.scal.as<double>());
+    KERNEL_CHECK();
+    return SYMGPU_OK;
+}
+
+// *re_out = Re<v, w> in the fixed order (matvec.h): one inner product, the chunk sums in `partial`, the total in *h
+int lz_inner(const f64x2 *v, const f64x2 *w, u64 N, f64x2 *partial, f64x2 *h, double *re_out) {
+    hipStream_t st = ctx().stream;
+    const unsigned chunks = lz_chunks(N);
+    hipLaunchKernelGGL(k_lz_dots, dim3(chunks, 1u), dim3(LZ_WG), 0, st, v, N, lz_chunk(N), 1, w, partial);
+    hipLaunchKernelGGL(k_lz_reduce, dim3(1), dim3(LZ_WG), 0, st, partial, chunks, 1, h, 0, 0, re_out);
     KERNEL_CHECK();
     return SYMGPU_OK;
 }

@@ -831,6 +831,98 @@ def vec_combine(basis, m, n_qubits, s, out=None, normalise=False):
     check(_lib.lib().symgpu_vec_combine(basis.ptr, int(m), int(n_qubits), addr(s), (basis if out is None else out).ptr, 1 if normalise else 0))
 
 
+# ---- exp(i theta P) rotations of a statevector, energy, adjoint gradient, pool gradient (csrc/ansatz.hip) --------------------------------
+ANSATZ_DIRECT, ANSATZ_TILED = 1, 2           # SYMGPU_ANSATZ_*: the forms an ansatz_apply reports as a bit set (0: no rotation ran)
+
+
+def _cos_sin(x, count):
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    if x.shape[0] != count:
+        raise ValueError(f'ansatz: {x.shape[0]} angles for {count} generators')
+    return np.ascontiguousarray(np.cos(x)), np.ascontiguousarray(np.sin(x))
+
+
+class AnsatzPlan:
+    """Owner of a ``symgpu_ansatz_plan``: the rows of a device operator of 1 .. 32 qubits as the generators ``P_k`` of
+    ``prod_k exp(i theta_k P_k)``, in operator order, resident until ``free()`` (also on leaving a ``with`` block, or when collected).
+    The operator itself is not referenced after the constructor returns."""
+
+    def __init__(self, devop, n_qubits):
+        n_qubits = int(n_qubits)
+        if not 1 <= n_qubits <= 32:
+            raise ValueError(f'ansatz: n_qubits = {n_qubits} outside 1 .. 32')
+        self.handle = ctypes.c_void_p()
+        rc = _lib.lib().symgpu_ansatz_plan(devop.handle, n_qubits, ctypes.byref(self.handle))
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        check(rc)
+        self.n_qubits = n_qubits
+        self.n_generators = self.info()[1]
+
+    def info(self):
+        """(n_qubits, n_generators, n_runs, device_bytes)."""
+        n, k, r, b = c_int(0), c_i64(0), c_i64(0), c_i64(0)
+        check(_lib.lib().symgpu_ansatz_info(self.handle, ctypes.addressof(n), ctypes.addressof(k), ctypes.addressof(r), ctypes.addressof(b)))
+        return n.value, k.value, r.value, b.value
+
+    def apply(self, x, psi, k_begin=0, k_end=None, inverse=False):
+        """Rotations ``k_begin .. k_end-1`` (default: all) with the angles ``x`` (one per generator of the plan) on ``psi``, a
+        ``DeviceBuffer`` of ``2^n`` complex128, in place.  ``inverse``: the inverse rotations in reverse order.  Returns the forms that
+        ran, ``ANSATZ_DIRECT | ANSATZ_TILED`` as a bit set (``SYMGPU_ANSATZ_FORM=direct`` forces direct passes; the bits are the same)."""
+        k_end = self.n_generators if k_end is None else int(k_end)
+        cos_t, sin_t = _cos_sin(x, self.n_generators)
+        if inverse:
+            sin_t = -sin_t
+        form = c_int(0)
+        check(_lib.lib().symgpu_ansatz_apply(self.handle, addr(cos_t), addr(sin_t), int(k_begin), k_end, 1 if inverse else 0, psi.ptr,
+                                             ctypes.addressof(form)))
+        return form.value
+
+    def energy_grad(self, plan_H, x, ref, psi_out=None, want_grad=True):
+        """``(E, grad)`` of ``<psi(x)|H|psi(x)>`` for ``psi(x)`` prepared from ``ref`` (``DeviceBuffer``, not changed): one state
+        preparation, one ``H v`` and one reverse sweep.  ``grad`` is None without ``want_grad``; ``psi_out`` (``DeviceBuffer`` or
+        None) receives the prepared state."""
+        cos_t, sin_t = _cos_sin(x, self.n_generators)
+        energy = ctypes.c_double(0)
+        grad = np.zeros(self.n_generators, dtype=np.float64) if want_grad else None
+        rc = _lib.lib().symgpu_ansatz_energy_grad(self.handle, plan_H.handle, addr(cos_t), addr(sin_t), ref.ptr,
+                                                  None if psi_out is None else psi_out.ptr, ctypes.addressof(energy), addr(grad))
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        check(rc)
+        return energy.value, grad
+
+    def free(self):
+        if self.handle is not None and self.handle.value:
+            _lib.load().symgpu_ansatz_free(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def pool_gradient(plan_H, pool_devop, psi, want_energy=False):
+    """``<psi| i [H, P_j] |psi>`` for every row ``P_j`` of the device operator ``pool_devop`` from one ``H psi`` (``psi``: a
+    ``DeviceBuffer`` of ``2^n`` complex128).  With ``want_energy``: ``(gradient, <psi|H|psi>)``."""
+    grad = np.zeros(pool_devop.n_terms, dtype=np.float64)
+    energy = ctypes.c_double(0)
+    rc = _lib.lib().symgpu_pool_gradient(plan_H.handle, pool_devop.handle, psi.ptr, ctypes.addressof(energy) if want_energy else None, addr(grad))
+    if rc == _lib.E_NOMEM:
+        raise MemoryError(_lib.last_error())
+    check(rc)
+    return (grad, energy.value) if want_energy else grad
+
+
 def mem_info():
     """(free, total) bytes of the current device."""
     free_b, total_b = c_i64(0), c_i64(0)
