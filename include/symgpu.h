@@ -529,6 +529,43 @@ int symgpu_ansatz_energy_grad(struct symgpu_ansatz_s *plan, struct symgpu_matvec
 int symgpu_pool_gradient(struct symgpu_matvec_s *plan_H, symgpu_op_t pool, const double *psi_dev, double *energy /* or NULL */,
                          double *grad_host /* [M] */);
 
+/* ---- f9: the reduced density matrix of a dense statevector (symmer/operators/base.py:2025-2054 QuantumState.partial_trace_over_qubits,
+ * get_rdm; symmer/utils.py:78-94 get_entanglement_entropy; csrc/rdm.hip).  Conventions of f7 / f8: qubit q is bit n-1-q of a basis index
+ * b.  kept_host: the k kept qubits, strictly ascending.  The row index a of rho carries the kept qubits with the lowest qubit number as
+ * its most significant bit, e carries the traced qubits the same way, b(a, e) is the index with both in place, and
+ *   rho[a][a'] = sum_e psi[b(a, e)] conj psi[b(a', e)]
+ * psi_dev: complex128 [2^n] (symgpu_dev_alloc), not normalised by the call and not written.  rho_dev: complex128 [2^k][2^k], row-major.
+ * n_qubits 1 .. 32, k 0 .. min(n_qubits, 12) — a refusal bound that keeps the matrix to 256 MiB and a host eigensolve possible, not a
+ * performance claim.  k = 0 gives the 1 x 1 matrix <psi|psi>, k = n gives psi psi^+.  SYMGPU_E_INVALID, before anything is allocated and
+ * with psi and rho untouched: n_qubits or k outside the range, kept_host not strictly ascending or outside 0 .. n-1, a null psi_dev,
+ * rho_dev or kept_host (kept_host may be NULL when k = 0), rho_dev overlapping psi_dev.
+ * Result: only a <= a' is summed and rho[a'][a] is written as the exact conjugate of rho[a][a'], so rho is Hermitian to the bit; the
+ * diagonal is sum_e (re^2 + im^2) with imaginary part +0.0.  One multiply-add, with p = psi[b(a, e)], q = psi[b(a', e)]:
+ *   re <- fma(p.im, q.im, fma(p.re, q.re, re)),  im <- fma(-p.re, q.im, fma(p.im, q.re, im))      (the diagonal: re only)
+ * No floating-point atomics; every sum runs in an order fixed by (n, kept) and the form: two calls give the same bytes.
+ * Two forms, chosen once per call from (n, k); global reads go in index order in both (pieces of at least 2^4 amplitudes = 256 bytes
+ * whatever the kept set is), the kept / traced split is applied when LDS is indexed:
+ *   SYMGPU_RDM_STREAM (k <= KS = 3): one pass over psi.  The tile bits are the kept bits and the min(8, n-k) lowest traced index bits; a
+ *     workgroup stages a tile in LDS and thread t takes e = tile 2^min(8, n-k) + t, its 2^k amplitudes and the upper triangle in
+ *     registers.  The tiles are cut into C = min(tiles, 1024) chunks of consecutive tiles, one workgroup each, tiles ascending; the 256
+ *     thread sums of an entry are folded by halving (s[t] += s[t + 128], then 64, ... 1); one last launch adds the chunk sums to 0 in
+ *     ascending chunk order.  Scratch: C 2^k (2^k + 1) / 2 entries of 16 bytes.
+ *   SYMGPU_RDM_TILED (every other k): a Hermitian rank update on tiles of 64 x 64 entries, only the tile pairs I <= J.  e goes in blocks
+ *     of 2^min(4, n-k) values, the blocks in C chunks of consecutive blocks, C = min(blocks, the largest power of two <=
+ *     max(1, 1024 / pairs)) — a function of (n, k) only.  Workgroup (pair, chunk): per block the 64 x 2^4 panel of the row tile and of the
+ *     column tile (one panel on the diagonal) is staged in LDS, thread (ty, tx) of 16 x 16 adds to its 4 x 4 entries (rows ty + 16 i,
+ *     columns tx + 16 j), e ascending, from 0 (on a diagonal tile only to those with i <= j: the others lie below the diagonal for
+ *     every thread).  Chunk tiles go to scratch [C][2^k][2^k] (C 4^k 16 bytes, at most 256 MiB); one launch adds
+ *     them to 0 in ascending chunk order and writes both triangles.
+ * SYMGPU_RDM_FORM=stream|tiled (read on every call) forces a form where it is legal: tiled accepts every k, stream beyond KS is ignored.
+ * info (int64 [6] or NULL): [0] the form that ran, [1] KS, [2] C, [3] the tile edge (64; 0 for STREAM), [4] the workgroups of the
+ * accumulating launch, [5] the scratch bytes.  The device memory is checked before it is allocated (SYMGPU_E_NOMEM); the scratch is freed
+ * before the call returns, also on failure.  The call runs on the calling thread's CURRENT device. */
+#define SYMGPU_RDM_STREAM 1
+#define SYMGPU_RDM_TILED 2
+int symgpu_rdm(const double *psi_dev, int n_qubits, const int *kept_host, int k, double *rho_dev /* complex128 [2^k][2^k], row-major */,
+               int64_t *info /* [6] or NULL */);
+
 /* ---- f6: PauliwordOp.from_matrix (base.py:239-425), the inverse of f5: the Pauli decomposition of a 2^n x 2^n matrix M, n_qubits 1 .. 31
  * (csrc/pauli_decomp.hip).  With the conventions of f5 (qubit 0 the MOST significant bit of b, x, z):
  *   c(x, z) = i^{|x & z| mod 4} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]

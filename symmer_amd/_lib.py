@@ -129,6 +129,7 @@ SIGNATURES = {
     'symgpu_ansatz_apply': [P, P, P, c_i64, c_i64, c_int, P, P],
     'symgpu_ansatz_energy_grad': [P, P, P, P, P, P, P, P],
     'symgpu_pool_gradient': [P, P, P, P, P],
+    'symgpu_rdm': [P, c_int, P, c_int, P, P],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

@@ -1,5 +1,5 @@
 // matvec.h — what matvec.hip (the plan and y = H x), lanczos.hip (the vector kernels of the eigen-iteration) and ansatz.hip (rotations
-// exp(i theta P) on a statevector, energy and gradients) share.
+// exp(i theta P) on a statevector, energy and gradients) share; rdm.hip takes the memory check.
 #pragma once
 #include "xgroups.h"
 

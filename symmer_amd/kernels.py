@@ -923,6 +923,50 @@ def pool_gradient(plan_H, pool_devop, psi, want_energy=False):
     return (grad, energy.value) if want_energy else grad
 
 
+# ---- the reduced density matrix of a dense statevector (csrc/rdm.hip) -----------------------------------------------------------------
+RDM_STREAM, RDM_TILED = 1, 2                 # SYMGPU_RDM_*: the form a symgpu_rdm reports in info[0]
+RDM_MAX_QUBITS, RDM_MAX_KEPT = 32, 12        # the refusal bounds of symgpu_rdm
+
+
+def rdm_dev(psi, n_qubits, kept, want_info=False):
+    """The reduced density matrix of the ``2^n`` amplitudes ``psi`` (a ``DeviceBuffer``, or a complex array that is uploaded; qubit 0
+    the most significant bit of the index) over the qubits ``kept`` — any iterable of ints, de-duplicated and sorted as the reference's
+    ``get_rdm`` does through a set — as complex128 ``[2^k, 2^k]``; ``psi`` is not normalised.  The matrix is Hermitian to the bit.
+    ``SYMGPU_RDM_FORM=stream|tiled`` forces a form where it is legal.  With ``want_info``: ``(rho, info)``, ``info`` the six int64 words of
+    ``symgpu_rdm`` (form, KS, chunks, tile edge, workgroups, scratch bytes).  ValueError for a qubit outside ``0 .. n-1``, more than 32
+    qubits or more than 12 kept ones; MemoryError when the scratch does not fit the device."""
+    n_qubits = int(n_qubits)
+    if not 1 <= n_qubits <= RDM_MAX_QUBITS:
+        raise ValueError(f'rdm: n_qubits = {n_qubits} outside 1 .. {RDM_MAX_QUBITS}')
+    qubits = sorted({int(q) for q in kept})
+    if any(q < 0 or q >= n_qubits for q in qubits):
+        raise ValueError(f'rdm: qubits {[q for q in qubits if q < 0 or q >= n_qubits]} outside 0 .. {n_qubits - 1}')
+    k = len(qubits)
+    if k > RDM_MAX_KEPT:
+        raise ValueError(f'rdm: {k} kept qubits; at most {RDM_MAX_KEPT} are supported (a {1 << RDM_MAX_KEPT} x {1 << RDM_MAX_KEPT} matrix)')
+    kept_arr = np.ascontiguousarray(qubits, dtype=np.int32)
+    info = np.zeros(6, dtype=np.int64)
+    own = None
+    if not isinstance(psi, DeviceBuffer):
+        host = np.ascontiguousarray(psi, dtype=np.complex128).reshape(-1)
+        if host.shape[0] != 1 << n_qubits:
+            raise ValueError(f'rdm: the vector has {host.shape[0]} elements, 2^{n_qubits} wanted')
+        psi = own = DeviceBuffer.upload(host)
+    try:
+        if psi.nbytes < 16 << n_qubits:
+            raise ValueError(f'rdm: the buffer holds {psi.nbytes} bytes, 2^{n_qubits} amplitudes need {16 << n_qubits}')
+        with DeviceBuffer(16 << (2 * k)) as rho:
+            rc = _lib.lib().symgpu_rdm(psi.ptr, n_qubits, addr(kept_arr) if k else None, k, rho.ptr, addr(info))
+            if rc == _lib.E_NOMEM:
+                raise MemoryError(_lib.last_error())
+            check(rc)
+            out = rho.download(np.complex128, 1 << (2 * k)).reshape(1 << k, 1 << k)
+    finally:
+        if own is not None:
+            own.free()
+    return (out, info) if want_info else out
+
+
 def mem_info():
     """(free, total) bytes of the current device."""
     free_b, total_b = c_i64(0), c_i64(0)

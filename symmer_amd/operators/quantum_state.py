@@ -3,8 +3,9 @@
 A sparse statevector is carried as a ``PauliwordOp`` (``|0> -> Z``, ``|1> -> X``, base.py:1564-1580), so applying an operator
 to a state is the SAME device path as operator x operator: the fused all-pairs product + cleanup kernel, followed by the
 ``i^{Y}`` post-factor (base.py:854-857).  Expectation values reuse it (base.py:796-819, 2438-2471).
-Sparse and dense vectors (``to_sparse_matrix``, ``to_dense_matrix``, base.py:1994-2023) are host code.  Not provided (sampling,
-partial traces, plotting): outside the accelerated path.
+Sparse and dense vectors (``to_sparse_matrix``, ``to_dense_matrix``, base.py:1994-2023) are host code.  Reduced density matrices
+(``partial_trace_over_qubits``, ``get_rdm``, base.py:2025-2054) are one device call on the dense amplitudes, ``rho = M M^+`` of
+``csrc/rdm.hip`` (up to 32 qubits, up to 12 kept).  Not provided (sampling, plotting): outside the accelerated path.
 """
 from copy import deepcopy
 from functools import cached_property
@@ -192,6 +193,39 @@ class QuantumState:
     def to_dense_matrix(self) -> np.ndarray:
         """base.py:2016-2023: ``to_sparse_matrix`` as a dense ndarray of the same shape."""
         return self.to_sparse_matrix.toarray()
+
+    def _rdm_over(self, kept, what: str) -> np.ndarray:
+        from .. import kernels
+        n = self.n_qubits
+        if not 1 <= n <= kernels.RDM_MAX_QUBITS:
+            raise ValueError(f'{what}: {n} qubits; 1 .. {kernels.RDM_MAX_QUBITS} are supported (a dense vector of 2^n amplitudes)')
+        if len(kept) > kernels.RDM_MAX_KEPT:
+            raise ValueError(f'{what}: {len(kept)} qubits remain; at most {kernels.RDM_MAX_KEPT} are supported '
+                             f'(a {1 << kernels.RDM_MAX_KEPT} x {1 << kernels.RDM_MAX_KEPT} matrix)')
+        return kernels.rdm_dev(np.asarray(self.to_dense_matrix).reshape(-1), n, kept)
+
+    def partial_trace_over_qubits(self, qubits: List[int] = []) -> np.ndarray:
+        """base.py:2025-2039: the reduced density matrix of the qubits that remain when ``qubits`` are traced out, complex128
+        ``[2^k, 2^k]`` with the remaining qubit of the lowest number as the most significant bit of the row and column index (the
+        reference's ``tensordot`` of the ``[2] * n`` amplitudes with their conjugate over ``qubits``), computed on the device
+        (``csrc/rdm.hip``).  The amplitudes are those of ``to_dense_matrix``: a bra gives the conjugate matrix, repeated basis strings add,
+        nothing is normalised.  ValueError for a repeated or out-of-range entry of ``qubits``, beyond 32 qubits, or when more than 12
+        qubits remain."""
+        qubits = [int(q) for q in qubits]
+        if len(set(qubits)) != len(qubits):
+            raise ValueError(f'partial_trace_over_qubits: repeated qubit in {qubits}')
+        if any(q < 0 or q >= self.n_qubits for q in qubits):
+            raise ValueError(f'partial_trace_over_qubits: qubits {qubits} outside 0 .. {self.n_qubits - 1}')
+        return self._rdm_over(sorted(set(range(self.n_qubits)) - set(qubits)), 'partial_trace_over_qubits')
+
+    def get_rdm(self, qubits: List[int] = []) -> np.ndarray:
+        """base.py:2041-2054: the reduced density matrix over ``qubits`` (the others are traced out); order and repeats in ``qubits`` are
+        ignored, as the reference's set does.  See ``partial_trace_over_qubits``; ValueError for a qubit outside ``0 .. n-1``, beyond 32
+        qubits, or for more than 12 kept qubits."""
+        kept = sorted({int(q) for q in qubits})
+        if any(q < 0 or q >= self.n_qubits for q in kept):
+            raise ValueError(f'get_rdm: qubits {list(qubits)} outside 0 .. {self.n_qubits - 1}')
+        return self._rdm_over(kept, 'get_rdm')
 
     def _is_normalized(self) -> bool:
         return bool(np.isclose(np.linalg.norm(self.state_op.cleanup().coeff_vec), 1))

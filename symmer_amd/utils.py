@@ -1,7 +1,10 @@
 """``exact_gs_energy`` (reference ``symmer/utils.py:14-76``) without the matrix: a Lanczos iteration with full reorthogonalisation whose
 vectors stay on the device.  ``H v`` is the matrix-free product of ``csrc/matvec.hip``; a step (product, Gram-Schmidt done twice, norm,
 next vector) is one call of ``csrc/lanczos.hip`` that returns two scalars; Python keeps the small tridiagonal matrix and takes its lowest
-eigenpair with NumPy."""
+eigenpair with NumPy.
+
+``get_entanglement_entropy`` (reference ``symmer/utils.py:78-94``): the reduced density matrix of the smaller side of the bipartition is
+one device call on the dense amplitudes (``csrc/rdm.hip``); its small Hermitian eigenproblem is NumPy's."""
 import numpy as np
 
 from . import kernels
@@ -129,4 +132,34 @@ def exact_gs_energy(H, initial_guess=None, n_particles=None, number_operator=Non
         finally:
             if keep is not None:
                 keep.free()
+
+
+def get_entanglement_entropy(psi, qubits):
+    """symmer/utils.py:78-94: the von Neumann entropy ``-sum lambda ln lambda`` of the bipartition ``qubits`` | the rest, over the positive
+    eigenvalues of the reduced density matrix.  ``psi`` is a ``QuantumState``, or ``2^n`` amplitudes (qubit 0 the most significant bit of
+    the index) as ``exact_gs_energy`` returns with ``return_array=True``; it is not normalised, as in the reference.  The matrix comes from
+    the device (``csrc/rdm.hip``) and is Hermitian to the bit, so the eigenvalues are ``numpy.linalg.eigvalsh``'s.  It is taken over
+    whichever of ``qubits`` and its complement is smaller — the non-zero spectra of ``M M^+`` and ``M^+ M`` are equal, so the value is the
+    same.  ValueError for a qubit outside ``0 .. n-1``, beyond 32 qubits, or when the smaller side has more than 12 qubits."""
+    if isinstance(psi, QuantumState):
+        n = psi.n_qubits
+        if not 1 <= n <= kernels.RDM_MAX_QUBITS:
+            raise ValueError(f'get_entanglement_entropy: {n} qubits; 1 .. {kernels.RDM_MAX_QUBITS} are supported')
+    else:
+        psi = np.asarray(psi, dtype=np.complex128).reshape(-1)
+        n = int(psi.shape[0]).bit_length() - 1
+        if psi.shape[0] != 1 << n or not 1 <= n <= kernels.RDM_MAX_QUBITS:
+            raise ValueError(f'get_entanglement_entropy: {psi.shape[0]} amplitudes; 2^n for n in 1 .. {kernels.RDM_MAX_QUBITS} wanted')
+    kept = {int(q) for q in qubits}
+    if any(q < 0 or q >= n for q in kept):
+        raise ValueError(f'get_entanglement_entropy: qubits {sorted(kept)} outside 0 .. {n - 1}')
+    if len(kept) > n - len(kept):
+        kept = set(range(n)) - kept
+    if len(kept) > kernels.RDM_MAX_KEPT:
+        raise ValueError(f'get_entanglement_entropy: the smaller side of the bipartition has {len(kept)} qubits; at most '
+                         f'{kernels.RDM_MAX_KEPT} are supported')
+    amplitudes = np.asarray(psi.to_dense_matrix).reshape(-1) if isinstance(psi, QuantumState) else psi
+    eigvals = np.linalg.eigvalsh(kernels.rdm_dev(amplitudes, n, kept))
+    eigvals = eigvals[eigvals > 0]
+    return float(-np.sum(eigvals * np.log(eigvals)))
 
