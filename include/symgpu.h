@@ -566,6 +566,78 @@ int symgpu_pool_gradient(struct symgpu_matvec_s *plan_H, symgpu_op_t pool, const
 int symgpu_rdm(const double *psi_dev, int n_qubits, const int *kept_host, int k, double *rho_dev /* complex128 [2^k][2^k], row-major */,
                int64_t *info /* [6] or NULL */);
 
+/* ---- f10: measuring a statevector (symmer/operators/base.py:2070-2096 QuantumState.sample_state, :2188-2212
+ * measure_state_in_computational_basis, :2474 ff. change_of_basis_XY_to_Z; csrc/sample.hip, csrc/basis.hip).  Conventions of f7 - f9:
+ * qubit q is bit n-1-q of a basis index, amplitudes are complex128, no floating-point atomics, every sum in the order stated here, two
+ * calls with the same input give the same bytes.  Every call runs on the calling thread's CURRENT device (a plan: on the plan's).
+ *
+ * Uniforms.  symgpu_philox_uniform writes draws first_draw .. first_draw + count - 1 of the stream of `seed` to out_dev (double [count]).
+ *   Draw s (counted from 0) is word s mod 4 of the Philox4x64-10 block with key (seed, 0) and counter (s div 4 + 1, 0, 0, 0); the double
+ *   is (word >> 11) * 2^-53.  Philox4x64-10: ten rounds (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))
+ *   with the multipliers M0 = 0xD2E7470EE14C6C93, M1 = 0xCA5A826395121157 (hi / lo: the halves of the 128-bit product), the key advanced
+ *   between rounds by the Weyl constants k0 += 0x9E3779B97F4A7C15, k1 += 0xBB67AE8584CAA73B.  This is, bit for bit, the stream of
+ *   numpy.random.Generator(numpy.random.Philox(key=seed, counter=0)).random(): a draw is a pure function of (seed, s), so launches,
+ *   batches and the offset carry no state.  SYMGPU_E_INVALID: a null out_dev, a negative first_draw or count, first_draw + count >= 2^63.
+ *
+ * Plan.  symgpu_sample_plan takes m >= 1 amplitudes (any m up to 2^40, not only a power of two) at amp_dev, which the plan REFERENCES
+ *   and never writes: the caller keeps them alive and unchanged until symgpu_sample_free.  The weight is w[i] = re re + im im: two
+ *   products and one sum, each rounded once, nothing contracted.  Above the weights sits a radix-16 tree: an entry of level j+1 is the sum
+ *   of its (up to 16) consecutive children of level j, added to 0 in ascending order; level 0 is the weights, the levels repeat until one
+ *   entry, the total, remains (m = 1: one level above the weight).  Levels >= 1 are stored (about m / 15 doubles, 1/30 of the vector's
+ *   bytes); the weights are recomputed from the amplitudes.  The plan is built with ONE read of the vector (a workgroup reads 4,096
+ *   amplitudes and writes their entries of levels 1, 2, 3; each further level is formed from the one below).  A total that is zero,
+ *   negative or not finite (an all-zero vector, a NaN or an infinite amplitude) is SYMGPU_E_INVALID, as are a null pointer and m < 1; the
+ *   tree is freed before the refusal returns.  symgpu_sample_info: *total (or NULL) the root; info (int64 [6] or NULL): [0] m, [1] the tree
+ *   depth (stored levels), [2] the plan's device bytes, [3] the launches that built it, [4] the counting form of the last draw
+ *   (SYMGPU_SAMPLE_HIST | SYMGPU_SAMPLE_SORT, 0: none), [5] the launches of the last draw in csrc/sample.hip (the scan and the sort add theirs).
+ *
+ * Draw.  With the uniform u of a draw, r = u * total (one rounding); walk down from the root.  At a node with children c_0 .. c_15 form
+ *   acc_0 = c_0, acc_k = acc_{k-1} + c_k — the partial sums of the construction, in its order — and take the first k with r < acc_k; then
+ *   r <- r - acc_{k-1} (r unchanged for k = 0).  FALLBACK: if no k qualifies (rounding at the right edge, or a parent's rounded partial sum
+ *   admitted slightly more than the child holds) take the last child with c_k > 0 and apply the same subtraction.  At level 0 the child
+ *   index is the sample.  A sample always has w > 0.  Against the exact inverse CDF the scheme is biased by the order of 2^-53 relative
+ *   per boundary (each boundary is a rounded partial sum).  symgpu_sample_draw: n_samples draws, 0 <= n_samples < 2^31; draw i uses
+ *   u_dev[i] (caller's uniforms in [0, 1), double [n_samples]) when u_dev is not NULL, else draw first_draw + i of the Philox stream of
+ *   `seed`.  order_dev (int64 [n_samples] or NULL) receives the sample of every draw in draw order.  idx_dev / count_dev (int64, capacity
+ *   min(m, n_samples) each) receive the distinct samples, ascending, with their counts; *n_distinct their number.  Two counting forms
+ *   give identical bytes: SYMGPU_SAMPLE_HIST (integer atomics into m 32-bit counters, then a compaction with the library's scan; m < 2^31)
+ *   and SYMGPU_SAMPLE_SORT (the library's radix sort of the draws, keys only, then run lengths).  The rule, in one place, compares bytes
+ *   moved — HIST where 28 m + 8 n_samples <= 24 P n_samples, P = the bytes of m - 1 —; SYMGPU_SAMPLE_COUNT=hist|sort (read on every call)
+ *   forces a form where it is legal.  SYMGPU_E_INVALID before anything is allocated: a null plan, idx_dev, count_dev or n_distinct,
+ *   n_samples outside the range, a negative first_draw, first_draw + n_samples >= 2^63.  n_samples = 0 launches nothing, *n_distinct = 0.
+ *
+ * Basis.  symgpu_basis_change applies, in place on psi_dev (complex128 [2^n], n_qubits 1 .. 32), H on the qubits of x_mask and H S^+ on
+ *   those of y_mask (bit q of a mask = qubit q; the masks disjoint and within n qubits, else SYMGPU_E_INVALID), so that U P U^+ = +Z on
+ *   every measured qubit of P (H X H = Z, H S^+ Y S H = Z); other qubits are untouched.  On the pair (a0, a1) of a measured index bit (a1:
+ *   the bit set): on a Y-qubit first a1 <- (a1.im, -a1.re) (S^+, exact); then a0' = (a0 + a1) r, a1' = (a0 - a1) r per component, each
+ *   sum and product rounded once, r = 0x3FE6A09E667F3BCD (0x1.6a09e667f3bcdp-1), the double nearest 1/sqrt 2.  ORDER (it changes the bits):
+ *   the measured qubits in descending qubit number, which is ascending index bit.  SYMGPU_BASIS_DIRECT: one launch per measured qubit over
+ *   the 2^(n-1) pairs.  SYMGPU_BASIS_TILED (the default): the measured bits go, ascending, into groups, one pass over the vector per group;
+ *   the tile rule of symgpu_ansatz_apply: a group's tile bits are the 4 lowest index bits and its measured bits while the tile holds
+ *   <= 2^12 amplitudes (64 KiB of LDS), filled with the lowest free bits up to min(n, 10); the butterflies run in LDS in the same order
+ *   with a barrier between them.  Both forms give the same bits.  SYMGPU_BASIS_FORM=direct (read on every call) forces direct passes.
+ *   *form (or NULL): the form that ran, 0 when both masks are empty.
+ *
+ * Estimates.  symgpu_counts_signed_sums: out_host[k] = sum_j count_j (-1)^{|z_k & b_j|} (int64, exact, independent of order) for every
+ *   row k of a resident operator (Wq = 1, n_qubits 1 .. 32) over the n_distinct basis indices b_j = idx_dev[j] with counts count_dev[j];
+ *   packed rows carry qubit q at bit q, basis indices at bit n-1-q: the call reverses z_k.  A row with a non-empty X-part is
+ *   SYMGPU_E_INVALID (out_host untouched).  One read-back of T integers (and the X flag).
+ * The device memory is checked before it is allocated (SYMGPU_E_NOMEM); scratch is freed before a call returns, also on failure. */
+#define SYMGPU_SAMPLE_HIST 1
+#define SYMGPU_SAMPLE_SORT 2
+#define SYMGPU_BASIS_DIRECT 1
+#define SYMGPU_BASIS_TILED 2
+struct symgpu_sample_s;   /* a plan: opaque, owned by the caller between symgpu_sample_plan and symgpu_sample_free */
+int symgpu_philox_uniform(uint64_t seed, int64_t first_draw, int64_t count, double *out_dev);
+int symgpu_sample_plan(const double *amp_dev, int64_t m, struct symgpu_sample_s **plan);
+int symgpu_sample_free(struct symgpu_sample_s *plan);
+int symgpu_sample_info(struct symgpu_sample_s *plan, double *total /* or NULL */, int64_t *info /* [6] or NULL */);
+int symgpu_sample_draw(struct symgpu_sample_s *plan, int64_t n_samples, uint64_t seed, int64_t first_draw, const double *u_dev /* or NULL */,
+                       int64_t *order_dev /* [n_samples] or NULL */, int64_t *idx_dev, int64_t *count_dev, int64_t *n_distinct);
+int symgpu_basis_change(double *psi_dev, int n_qubits, uint64_t x_mask, uint64_t y_mask, int *form /* or NULL */);
+int symgpu_counts_signed_sums(symgpu_op_t op, int n_qubits, const int64_t *idx_dev, const int64_t *count_dev, int64_t n_distinct,
+                              int64_t *out_host /* [T] */);
+
 /* ---- f6: PauliwordOp.from_matrix (base.py:239-425), the inverse of f5: the Pauli decomposition of a 2^n x 2^n matrix M, n_qubits 1 .. 31
  * (csrc/pauli_decomp.hip).  With the conventions of f5 (qubit 0 the MOST significant bit of b, x, z):
  *   c(x, z) = i^{|x & z| mod 4} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]

@@ -130,6 +130,13 @@ SIGNATURES = {
     'symgpu_ansatz_energy_grad': [P, P, P, P, P, P, P, P],
     'symgpu_pool_gradient': [P, P, P, P, P],
     'symgpu_rdm': [P, c_int, P, c_int, P, P],
+    'symgpu_philox_uniform': [c_u64, c_i64, c_i64, P],
+    'symgpu_sample_plan': [P, c_i64, PP],
+    'symgpu_sample_free': [P],
+    'symgpu_sample_info': [P, P, P],
+    'symgpu_sample_draw': [P, c_i64, c_u64, c_i64, P, P, P, P, P],
+    'symgpu_basis_change': [P, c_int, c_u64, c_u64, P],
+    'symgpu_counts_signed_sums': [P, c_int, P, P, c_i64, P],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

@@ -967,6 +967,187 @@ def rdm_dev(psi, n_qubits, kept, want_info=False):
     return (out, info) if want_info else out
 
 
+# ---- measuring a vector of amplitudes (csrc/sample.hip, csrc/basis.hip) ----------------------------------------------------------------
+SAMPLE_HIST, SAMPLE_SORT = 1, 2              # SYMGPU_SAMPLE_*: the counting form of a draw (info[4] of symgpu_sample_info)
+BASIS_DIRECT, BASIS_TILED = 1, 2             # SYMGPU_BASIS_*: the form a symgpu_basis_change reports
+SAMPLE_MAX_DRAWS = (1 << 31) - 1             # the refusal bound of symgpu_sample_draw
+
+
+def philox_uniforms(seed, first_draw, count, out=None):
+    """Draws ``first_draw .. first_draw + count - 1`` of the Philox4x64-10 stream of ``seed``, float64: the numbers of
+    ``np.random.Generator(np.random.Philox(key=seed, counter=0)).random()`` at those positions, generated on the device.  ``out``: a
+    ``DeviceBuffer`` that receives them (then nothing is downloaded and the buffer is returned)."""
+    count = int(count)
+    buf = out if out is not None else DeviceBuffer(max(8, 8 * max(count, 0)))
+    try:
+        check(_lib.lib().symgpu_philox_uniform(int(seed), int(first_draw), count, buf.ptr))
+        return buf if out is not None else buf.download(np.float64, count) if count else np.zeros(0, dtype=np.float64)
+    finally:
+        if out is None:
+            buf.free()
+
+
+class SamplePlan:
+    """Owner of a ``symgpu_sample_plan``: the radix-16 sum tree over the weights ``|a_i|^2`` of ``m`` complex128 amplitudes, resident
+    until ``free()`` (also on leaving a ``with`` block, or when collected).  ``amp``: a ``DeviceBuffer``, which the plan references and
+    keeps alive, or a host array, which is uploaded.  ValueError for weights that add up to zero or to something not finite."""
+
+    def __init__(self, amp, m=None):
+        self.handle, self._own = None, None
+        if not isinstance(amp, DeviceBuffer):
+            host = np.ascontiguousarray(amp, dtype=np.complex128).reshape(-1)
+            m = host.shape[0] if m is None else int(m)
+            if m < 1 or m > host.shape[0]:
+                raise ValueError(f'sample: m = {m} for {host.shape[0]} amplitudes')
+            amp = self._own = DeviceBuffer.upload(host)
+        m = amp.nbytes // 16 if m is None else int(m)
+        if m < 1 or 16 * m > amp.nbytes:
+            raise ValueError(f'sample: m = {m} amplitudes do not fit the buffer of {amp.nbytes} bytes')
+        self.amp, self.m = amp, m
+        handle = ctypes.c_void_p()
+        rc = _lib.lib().symgpu_sample_plan(amp.ptr, m, ctypes.byref(handle))
+        if rc != _lib.OK and self._own is not None:
+            self._own.free()
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        if rc == _lib.E_INVALID:
+            raise ValueError(_lib.last_error())
+        check(rc)
+        self.handle = handle
+
+    def _info(self):
+        total, info = ctypes.c_double(0), np.zeros(6, dtype=np.int64)
+        check(_lib.lib().symgpu_sample_info(self.handle, ctypes.addressof(total), addr(info)))
+        return total.value, info
+
+    @property
+    def total(self):
+        """The root of the tree: the sum of the weights in the tree's order."""
+        return self._info()[0]
+
+    def info(self):
+        """The six int64 words of ``symgpu_sample_info``: m, tree depth, device bytes, launches of the build, the counting form of the
+        last draw, its launches."""
+        return self._info()[1]
+
+    def draw(self, n_samples, seed=0, first_draw=0, u=None, want_order=False):
+        """``n_samples`` draws: ``(idx, count)``, the distinct samples ascending (int64) with their counts (int64); with ``want_order``
+        ``(idx, count, order)``, ``order`` the sample of every draw.  ``u``: the caller's uniforms (float64 ``[n_samples]`` or a
+        ``DeviceBuffer``) in place of the Philox stream of ``seed`` from ``first_draw`` on.  ``SYMGPU_SAMPLE_COUNT=hist|sort`` forces a
+        counting form where it is legal; both give the same arrays."""
+        n_samples = int(n_samples)
+        with DeviceBuffer(8 * max(1, n_samples) if want_order else 8) as order:
+            idx, cnt, nd = self.draw_dev(n_samples, seed, first_draw, u, order if want_order else None)
+            with idx, cnt:
+                if n_samples == 0:
+                    return (np.zeros(0, dtype=np.int64),) * (3 if want_order else 2)
+                out = (idx.download(np.int64, nd), cnt.download(np.int64, nd))
+            return out + (order.download(np.int64, n_samples),) if want_order else out
+
+    def draw_dev(self, n_samples, seed=0, first_draw=0, u=None, order=None):
+        """``draw`` with the results left on the device: ``(idx, count, n_distinct)``, two ``DeviceBuffer`` of int64 that the caller
+        frees.  ``order``: a ``DeviceBuffer`` of ``n_samples`` int64 that receives the sample of every draw, or None."""
+        n_samples = int(n_samples)
+        if not 0 <= n_samples <= SAMPLE_MAX_DRAWS:
+            raise ValueError(f'sample: n_samples = {n_samples} outside 0 .. 2^31 - 1')
+        cap = max(1, min(self.m, n_samples))
+        own_u = None
+        if u is not None and not isinstance(u, DeviceBuffer):
+            u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+            if u.shape[0] != n_samples:
+                raise ValueError(f'sample: {u.shape[0]} uniforms for {n_samples} draws')
+            u = own_u = DeviceBuffer.upload(u) if n_samples else None
+        idx, cnt = DeviceBuffer(8 * cap), DeviceBuffer(8 * cap)
+        try:
+            nd = c_i64(0)
+            rc = _lib.lib().symgpu_sample_draw(self.handle, n_samples, int(seed), int(first_draw), None if u is None else u.ptr,
+                                               None if order is None else order.ptr, idx.ptr, cnt.ptr, ctypes.addressof(nd))
+            if rc == _lib.E_NOMEM:
+                raise MemoryError(_lib.last_error())
+            check(rc)
+            return idx, cnt, nd.value
+        except BaseException:
+            idx.free()
+            cnt.free()
+            raise
+        finally:
+            if own_u is not None:
+                own_u.free()
+
+    def free(self):
+        if self.handle is not None and self.handle.value:
+            _lib.load().symgpu_sample_free(self.handle)
+        self.handle = None
+        if self._own is not None:
+            self._own.free()
+            self._own = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _qubit_mask(qubits, n_qubits, what):
+    mask = 0
+    for q in qubits:
+        q = int(q)
+        if not 0 <= q < n_qubits:
+            raise ValueError(f'{what}: qubit {q} outside 0 .. {n_qubits - 1}')
+        mask |= 1 << q
+    return mask
+
+
+def basis_change_dev(psi, n_qubits, x_qubits, y_qubits):
+    """``H`` on ``x_qubits`` and ``H S^+`` on ``y_qubits`` of the ``2^n`` amplitudes in the ``DeviceBuffer`` ``psi``, in place: afterwards a
+    Pauli with X on the former and Y on the latter reads as Z.  Returns the form that ran (``BASIS_DIRECT`` / ``BASIS_TILED``, 0: no qubit
+    named); ``SYMGPU_BASIS_FORM=direct`` forces direct passes, the bits are the same."""
+    n_qubits = int(n_qubits)
+    if not 1 <= n_qubits <= 32:
+        raise ValueError(f'basis_change: n_qubits = {n_qubits} outside 1 .. 32')
+    if psi.nbytes < 16 << n_qubits:
+        raise ValueError(f'basis_change: the buffer holds {psi.nbytes} bytes, 2^{n_qubits} amplitudes need {16 << n_qubits}')
+    xm, ym = _qubit_mask(x_qubits, n_qubits, 'basis_change'), _qubit_mask(y_qubits, n_qubits, 'basis_change')
+    if xm & ym:
+        raise ValueError('basis_change: a qubit is named for both H and H S^+')
+    form = c_int(0)
+    check(_lib.lib().symgpu_basis_change(psi.ptr, n_qubits, xm, ym, ctypes.addressof(form)))
+    return form.value
+
+
+def counts_signed_sums(devop, n_qubits, idx, count, n_distinct=None):
+    """``sum_j count_j (-1)^{|z_k & b_j|}`` for every row k of the Z-only device operator ``devop`` over the basis indices ``idx`` with the
+    counts ``count`` — int64 arrays, or two ``DeviceBuffer`` (as ``SamplePlan.draw_dev`` leaves them) with ``n_distinct`` entries —:
+    int64 ``[T]``, exact.  ValueError when a row has an X-part."""
+    if isinstance(idx, DeviceBuffer):
+        idx_buf, cnt_buf, n, own = idx, count, int(n_distinct), ()
+    else:
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.int64).reshape(-1)
+        assert idx.shape == count.shape
+        n = idx.shape[0]
+        idx_buf, cnt_buf = DeviceBuffer.upload(idx if n else np.zeros(1, np.int64)), DeviceBuffer.upload(count if n else np.zeros(1, np.int64))
+        own = (idx_buf, cnt_buf)
+    try:
+        out = np.zeros(devop.n_terms, dtype=np.int64)
+        rc = _lib.lib().symgpu_counts_signed_sums(devop.handle, int(n_qubits), idx_buf.ptr, cnt_buf.ptr, int(n), addr(out))
+        if rc == _lib.E_INVALID:
+            raise ValueError(_lib.last_error())
+        check(rc)
+        return out
+    finally:
+        for b in own:
+            b.free()
+
+
 def mem_info():
     """(free, total) bytes of the current device."""
     free_b, total_b = c_i64(0), c_i64(0)

@@ -4,5 +4,5 @@ from .utils import (symplectic_cleanup, matmul_GF2, mul_symplectic, _rref_binary
                     numba_dot_matmal_GF2)
 from .base import PauliwordOp
 from .independent_op import IndependentOp
-from .quantum_state import QuantumState, single_term_expval, term_expvals
+from .quantum_state import QuantumState, single_term_expval, term_expvals, change_of_basis_XY_to_Z
 from .noncontextual_op import NoncontextualOp, NoncontextualSolver

@@ -710,6 +710,12 @@ class PauliwordOp:
 
     def _clique_cover_device(self, relation: int, strategy: str) -> Dict[int, "PauliwordOp"]:
         dev = self._device()
+        return {k: PauliwordOp._from_device(kernels.op_gather(dev, members), self.n_qubits, len(members))
+                for k, members in enumerate(self._clique_members_device(relation, strategy))}
+
+    def _clique_members_device(self, relation: int, strategy: str) -> List[np.ndarray]:
+        """The device colouring as term indices: entry k holds the members of clique k in colouring order."""
+        dev = self._device()
         if strategy == 'sorted_insertion':
             order = self._ORDERINGS['magnitude'](self)
         else:
@@ -721,11 +727,7 @@ class PauliwordOp:
         by_colour = np.argsort(in_order, kind='stable')               # positions of the order, grouped by colour, colouring order within
         sizes = np.bincount(in_order, minlength=n_colours)
         ends = np.cumsum(sizes)
-        cliques = {}
-        for k in range(n_colours):
-            members = order[by_colour[ends[k] - sizes[k]:ends[k]]]
-            cliques[k] = PauliwordOp._from_device(kernels.op_gather(dev, members), self.n_qubits, len(members))
-        return cliques
+        return [order[by_colour[ends[k] - sizes[k]:ends[k]]] for k in range(n_colours)]
 
     def commutator(self, PwordOp: "PauliwordOp") -> "PauliwordOp":
         return self * PwordOp - PwordOp * self

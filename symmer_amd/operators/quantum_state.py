@@ -5,7 +5,10 @@ to a state is the SAME device path as operator x operator: the fused all-pairs p
 ``i^{Y}`` post-factor (base.py:854-857).  Expectation values reuse it (base.py:796-819, 2438-2471).
 Sparse and dense vectors (``to_sparse_matrix``, ``to_dense_matrix``, base.py:1994-2023) are host code.  Reduced density matrices
 (``partial_trace_over_qubits``, ``get_rdm``, base.py:2025-2054) are one device call on the dense amplitudes, ``rho = M M^+`` of
-``csrc/rdm.hip`` (up to 32 qubits, up to 12 kept).  Not provided (sampling, plotting): outside the accelerated path.
+``csrc/rdm.hip`` (up to 32 qubits, up to 12 kept).  Measurement (``sample_state``, ``sample_counts``, ``normalize_counts``,
+``measure_state_in_computational_basis``, ``change_of_basis_XY_to_Z``, base.py:1964-1975, 2070-2096, 2188-2212, 2474 ff.) draws on the
+device from a sum tree over the weights (``csrc/sample.hip``) and changes basis in place on the dense amplitudes (``csrc/basis.hip``).
+Not provided (plotting): outside the accelerated path.
 """
 from copy import deepcopy
 from functools import cached_property
@@ -229,6 +232,109 @@ class QuantumState:
 
     def _is_normalized(self) -> bool:
         return bool(np.isclose(np.linalg.norm(self.state_op.cleanup().coeff_vec), 1))
+
+    # ---- measurement (csrc/sample.hip, csrc/basis.hip) -------------------------------------------------------------------
+    @cached_property
+    def normalize_counts(self) -> "QuantumState":
+        """base.py:1964-1975: coefficients ``sqrt(c / sum c)`` — the state a table of counts stands for."""
+        coeff = self.state_op.coeff_vec
+        return QuantumState(self.state_matrix, np.sqrt(coeff / np.sum(coeff)), vec_type=self.vec_type)
+
+    @staticmethod
+    def _seed_of(seed) -> int:
+        """``seed`` itself, or one integer of NumPy's global generator (so that ``np.random.seed`` makes a run repeatable)."""
+        return int(np.random.randint(0, np.iinfo(np.int64).max, dtype=np.int64)) if seed is None else int(seed)
+
+    def sample_state(self, n_samples: int, return_normalized: bool = False, seed=None) -> "QuantumState":
+        """base.py:2070-2096: ``n_samples`` measurements in the computational basis, as a state on the same ``state_matrix`` (same
+        rows, same order, same ``vec_type``) whose coefficients are the counts — ``sqrt(count / n_samples)`` with
+        ``return_normalized``; a row never drawn keeps a 0.  The terms are sampled as they stand (no cleanup) with weights ``|c_i|^2``:
+        one sum tree over the T coefficients on the device and ``n_samples`` walks down it (``kernels.SamplePlan``), draw ``i`` from
+        uniform ``i`` of the Philox4x64-10 stream of ``seed`` — the numbers of ``np.random.Generator(np.random.Philox(key=seed))``.
+        ``seed=None`` takes one integer from NumPy's global generator.  ValueError for a state that is not normalised."""
+        from .. import kernels
+        if not self._is_normalized():
+            raise ValueError('should not sample state that is not normalized')
+        n_samples = int(n_samples)
+        counter = np.zeros(self.n_terms, dtype=np.int64)
+        with kernels.SamplePlan(np.asarray(self.state_op.coeff_vec, dtype=np.complex128)) as plan:
+            idx, count = plan.draw(n_samples, self._seed_of(seed))
+        counter[idx] = count
+        coeff = np.sqrt(counter / n_samples) if return_normalized else counter
+        return QuantumState(self.state_matrix, coeff, vec_type=self.vec_type)
+
+    def sample_counts(self, n_samples: int, seed=None):
+        """``n_samples`` measurements of the dense amplitudes (1 .. 32 qubits; repeated basis strings add, as in
+        ``to_dense_matrix``): ``(indices, counts)``, the distinct basis indices ascending (qubit 0 the most significant bit) and their
+        counts, both int64.  Nothing of size ``2^n`` exists on the host beyond the vector that is uploaded.  Seeds as in
+        ``sample_state``; ValueError for a state that is not normalised."""
+        from .. import kernels
+        if not 1 <= self.n_qubits <= 32:
+            raise ValueError(f'sample_counts: {self.n_qubits} qubits; 1 .. 32 are supported (a dense vector of 2^n amplitudes)')
+        if not self._is_normalized():
+            raise ValueError('should not sample state that is not normalized')
+        with kernels.SamplePlan(np.asarray(self.to_dense_matrix).reshape(-1)) as plan:
+            return plan.draw(int(n_samples), self._seed_of(seed))
+
+    def measure_state_in_computational_basis(self, P_op):
+        """base.py:2188-2212: ``(psi_new, Z_new)`` with ``<self|P_op|self> = <psi_new|Z_new|psi_new>``: ``psi_new = U |self>`` and
+        ``Z_new = U P_op U^+`` for the layer ``U`` of ``change_of_basis_XY_to_Z(P_op)`` — H on the qubits where the FIRST row of
+        ``P_op`` has X, H S^+ where it has Y.  Kets only.  The state goes through the device (``kernels.basis_change_dev`` on the dense
+        amplitudes, 1 .. 32 qubits) and ``from_array``; ``U`` itself is never built for it.  When the layer diagonalises every term —
+        each term qubitwise compatible with the first row and with no X or Y outside that row's — ``Z_new`` is written directly
+        (``z' = z | x``, ``x' = 0``, coefficients unchanged: H X H = Z, H S^+ Y S H = Z); otherwise it is the reference's
+        ``U * P_op * U.dagger`` on the product kernels."""
+        from .. import kernels
+        from .base import PauliwordOp
+        assert self.vec_type == 'ket', 'cannot perform change of basis on bra'
+        assert P_op.n_qubits == self.n_qubits, 'operator and state defined for different number of qubits'
+        n = self.n_qubits
+        if not 1 <= n <= 32:
+            raise ValueError(f'measure_state_in_computational_basis: {n} qubits; 1 .. 32 are supported (a dense vector of 2^n amplitudes)')
+        X, Z = np.asarray(P_op.X_block, dtype=bool), np.asarray(P_op.Z_block, dtype=bool)
+        x0, z0 = X[0], Z[0]
+        with kernels.DeviceBuffer.upload(np.asarray(self.to_dense_matrix, dtype=np.complex128).reshape(-1)) as psi:
+            kernels.basis_change_dev(psi, n, np.flatnonzero(x0 & ~z0), np.flatnonzero(x0 & z0))
+            psi_new = QuantumState.from_array(psi.download(np.complex128, 1 << n).reshape(-1, 1))
+        if not np.any(X & ~x0) and not np.any(X & (Z ^ z0)) and not np.any(~X & Z & x0):
+            Z_new = PauliwordOp(np.hstack([np.zeros_like(X), Z | X]), P_op.coeff_vec)
+        else:
+            U = change_of_basis_XY_to_Z(P_op)
+            Z_new = U * P_op * U.dagger
+        return psi_new, Z_new
+
+
+# one qubit of the layer in the Pauli basis (I, X, Y, Z), from H = (X + Z) / sqrt 2 and S^+ = ((1 - i) I + (1 + i) Z) / 2
+_LAYER_H = {'X': 1 / np.sqrt(2), 'Z': 1 / np.sqrt(2)}
+_LAYER_HSDG = {p: c / (2 * np.sqrt(2)) for p, c in (('I', 1 + 1j), ('X', 1 - 1j), ('Y', 1 - 1j), ('Z', 1 - 1j))}
+MAX_LAYER_QUBITS = 16
+
+
+def change_of_basis_XY_to_Z(P_op):
+    """base.py:2474 ff.: the operator ``U`` of H gates (where the first row of ``P_op`` has X) and H S^+ gates (where it has Y), with
+    ``U * P * U.dagger`` equal to that row with Z in place of every X and Y.  Host construction, term by term: a qubit with X gives the
+    two terms of ``(X + Z) / sqrt 2``, a qubit with Y the four of ``H S^+ = ((1 + i) I + (1 - i)(X + Y + Z)) / (2 sqrt 2)``, so ``U`` has
+    ``2^#X 4^#Y`` terms, in lexicographic order of the choices.  ValueError beyond 16 such qubits: the operator would have at least
+    65,536 terms and every product with it that many times the other operand's — ``measure_state_in_computational_basis`` applies the
+    layer to the state on the device without it."""
+    from .base import PauliwordOp
+    x0, z0 = np.asarray(P_op.X_block, dtype=bool)[0], np.asarray(P_op.Z_block, dtype=bool)[0]
+    measured = np.flatnonzero(x0)
+    if measured.size > MAX_LAYER_QUBITS:
+        raise ValueError(f'change_of_basis_XY_to_Z: {measured.size} qubits carry X or Y; beyond {MAX_LAYER_QUBITS} the operator has more '
+                         f'than 2^{MAX_LAYER_QUBITS} terms (measure_state_in_computational_basis applies the layer without building it)')
+    n = P_op.n_qubits
+    symp, coeff = np.zeros((1, 2 * n), dtype=bool), np.ones(1, dtype=np.complex128)
+    for q in measured:
+        table = _LAYER_HSDG if z0[q] else _LAYER_H
+        rows, cs = [], []
+        for pauli, c in table.items():
+            part = symp.copy()
+            part[:, q], part[:, n + q] = pauli in 'XY', pauli in 'YZ'
+            rows.append(part)
+            cs.append(coeff * c)
+        symp, coeff = np.vstack(rows), np.concatenate(cs)
+    return PauliwordOp(symp, coeff)
 
 
 def single_term_expval(P_op, psi: QuantumState) -> float:

@@ -4,7 +4,10 @@ next vector) is one call of ``csrc/lanczos.hip`` that returns two scalars; Pytho
 eigenpair with NumPy.
 
 ``get_entanglement_entropy`` (reference ``symmer/utils.py:78-94``): the reduced density matrix of the smaller side of the bipartition is
-one device call on the dense amplitudes (``csrc/rdm.hip``); its small Hermitian eigenproblem is NumPy's."""
+one device call on the dense amplitudes (``csrc/rdm.hip``); its small Hermitian eigenproblem is NumPy's.
+
+``sampled_expval``: the finite-shot estimate of ``<psi|H|psi>`` from measurements of the QWC cliques of ``H`` (``csrc/basis.hip``,
+``csrc/sample.hip``)."""
 import numpy as np
 
 from . import kernels
@@ -163,3 +166,63 @@ def get_entanglement_entropy(psi, qubits):
     eigvals = eigvals[eigvals > 0]
     return float(-np.sum(eigvals * np.log(eigvals)))
 
+
+
+def sampled_expval(H, psi, n_shots, seed=None, strategy='largest_first', return_terms=False):
+    """The finite-shot estimate of ``<psi|H|psi>``: what ``n_shots`` measurements per group of jointly measurable terms give, beside the
+    exact ``H.expval(psi)``.  ``H``: a ``PauliwordOp`` of 1 .. 32 qubits; ``psi``: a normalised ket ``QuantumState`` or its ``2^n``
+    amplitudes (qubit 0 the most significant bit of the index).
+
+    The terms are grouped into qubitwise-commuting cliques by the device colouring of ``clique_cover(edge_relation='QWC')``
+    (``strategy``: 'largest_first' or 'sorted_insertion').  ``psi`` is uploaded once; per clique ``g``, in the cover's order: a device
+    copy, one layer of H / H S^+ on the clique's merged X / Y positions (``csrc/basis.hip``), a sampling plan, ``n_shots`` draws from
+    uniforms ``g * n_shots ...`` of the Philox stream of ``seed`` (``csrc/sample.hip``), and the signed sums
+    ``sum_j count_j (-1)^{|z_k & b_j|}`` of the clique's terms read as Z strings; only those integers return.  The estimate of a term is
+    its sum over ``n_shots`` (the identity: 1) and the result ``sum_k c_k est_k`` (the real part for a Hermitian ``H``; complex
+    coefficients are kept).  ``seed=None`` takes one integer from NumPy's global generator.  With ``return_terms``:
+    ``(value, estimates, clique_of_term)``, both in ``H``'s term order."""
+    if not isinstance(H, PauliwordOp):
+        raise TypeError(f'sampled_expval: H must be a PauliwordOp ({type(H).__name__})')
+    n = H.n_qubits
+    if not 1 <= n <= 32:
+        raise ValueError(f'sampled_expval: {n} qubits; 1 .. 32 are supported')
+    if strategy not in ('largest_first', 'sorted_insertion'):
+        raise ValueError(f"sampled_expval: strategy {strategy!r}; 'largest_first' and 'sorted_insertion' run on the device")
+    n_shots = int(n_shots)
+    if n_shots < 1:
+        raise ValueError('sampled_expval: n_shots must be at least 1')
+    if isinstance(psi, QuantumState):
+        assert psi.vec_type == 'ket', 'sampled_expval: the state must be a ket'
+        if psi.n_qubits != n:
+            raise ValueError(f'sampled_expval: the state has {psi.n_qubits} qubits, the operator {n}')
+        amplitudes = np.asarray(psi.to_dense_matrix, dtype=np.complex128).reshape(-1)
+    else:
+        amplitudes = np.ascontiguousarray(psi, dtype=np.complex128).reshape(-1)
+        if amplitudes.shape[0] != 1 << n:
+            raise ValueError(f'sampled_expval: {amplitudes.shape[0]} amplitudes, 2^{n} wanted')
+    if not np.isclose(np.linalg.norm(amplitudes), 1):
+        raise ValueError('should not sample state that is not normalized')
+    seed = QuantumState._seed_of(seed)
+    T = H.n_terms
+    estimates, clique_of = np.zeros(T, dtype=np.float64), np.zeros(T, dtype=np.int64)
+    if T == 0:
+        return (0.0, estimates, clique_of) if return_terms else 0.0
+    from . import packing
+    X, Z = np.asarray(H.X_block, dtype=bool), np.asarray(H.Z_block, dtype=bool)
+    members = H._clique_members_device(kernels.RELATIONS['QWC'], strategy)
+    one = np.ones(1, dtype=np.float64)
+    with kernels.DeviceBuffer.upload(amplitudes) as psi_dev, kernels.DeviceBuffer(amplitudes.nbytes) as work:
+        for g, terms in enumerate(members):
+            kernels.vec_combine(psi_dev, 1, n, one, out=work)                              # work = 1.0 * psi: a copy to the bit
+            xg, zg = X[terms], Z[terms]
+            kernels.basis_change_dev(work, n, np.flatnonzero(np.any(xg & ~zg, axis=0)), np.flatnonzero(np.any(xg & zg, axis=0)))
+            z_rows = packing.pack_rows(np.hstack([np.zeros_like(xg), xg | zg]))
+            with kernels.SamplePlan(work, 1 << n) as plan, kernels.DeviceOp.upload(z_rows) as z_op:
+                idx, count, n_distinct = plan.draw_dev(n_shots, seed, g * n_shots)
+                with idx, count:
+                    sums = kernels.counts_signed_sums(z_op, n, idx, count, n_distinct)
+            estimates[terms] = sums / n_shots
+            clique_of[terms] = g
+    value = complex(np.sum(np.asarray(H.coeff_vec) * estimates))
+    value = value.real if np.allclose(np.asarray(H.coeff_vec).imag, 0) else value
+    return (value, estimates, clique_of) if return_terms else value
