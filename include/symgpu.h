@@ -638,6 +638,35 @@ int symgpu_basis_change(double *psi_dev, int n_qubits, uint64_t x_mask, uint64_t
 int symgpu_counts_signed_sums(symgpu_op_t op, int n_qubits, const int64_t *idx_dev, const int64_t *count_dev, int64_t n_distinct,
                               int64_t *out_host /* [T] */);
 
+/* ---- f11: a polynomial of H on a dense statevector, in the Chebyshev basis (symmer_amd/evolution/time_evolution.py evolve_state:
+ * exp(-i H t) psi and exp(-tau H) psi by the Chebyshev expansion; csrc/evolve.hip).  Conventions and the plan of f7.
+ * symgpu_cheb_apply   out = sum_{k=0..K} c_k T_k(H~) psi,  H~ = (H - centre) / half_width,  T_0 = 1, T_1 = x, T_k = 2 x T_{k-1} - T_{k-2}.
+ *   coef_host: double [K + 1][2] on the host, (re, im) of c_k.  psi_dev, out_dev: complex128 [2^n] device buffers, not the same one; psi
+ *   is never written.  SYMGPU_E_INVALID before anything is allocated: a null plan, coef_host, psi_dev or out_dev, psi_dev == out_dev,
+ *   K < 0, half_width not finite or <= 0, centre not finite.  The spectrum of H is the caller's business: outside
+ *   [centre - half_width, centre + half_width] the T_k grow exponentially in k.
+ *   Arithmetic — every operation below is one IEEE double operation rounded to nearest, nothing contracted, so that a NumPy restatement
+ *   on separate real and imaginary parts gives the same bits, and two calls give the same bytes.  h(v)[b] is the row sum that
+ *   symgpu_matvec_apply computes, in its order (groups in ascending x, D_g from its first term, the sum started from the first product;
+ *   +0.0 in both components for a plan without groups).  A complex product c v is the plain one of f7 with the coefficient in the place
+ *   of D:  (c.re v.re - c.im v.im,  c.re v.im + c.im v.re).  inv = 1.0 / half_width (one division, on the host), s_1 = inv, s_k = 2 inv.
+ *     T_0 = psi;                                        out[b] = c_0 psi[b]
+ *     t[b]   = h(T_{k-1})[b] - centre T_{k-1}[b]        per component: sub(h, mul(centre, v))
+ *     T_1[b] = s_1 t[b]                                 per component: mul(s_1, t)
+ *     T_k[b] = s_k t[b] - T_{k-2}[b]   (k >= 2)         per component: sub(mul(s_k, t), u)
+ *     out[b] = out[b] + c_k T_k[b]                      the complex product, then a componentwise add
+ *   Launches: one thread per row, 2^8 rows a workgroup, one launch per order k >= 1 (order 0 is folded into the first; K = 0 is one launch
+ *   of its own), all on the context's stream with one synchronise at the end.  Row b's thread alone reads and writes element b of
+ *   T_{k-2}, T_k and out, so T_k overwrites T_{k-2} in place except at k = 2, where T_0 is the caller's psi: two scratch vectors of
+ *   2^n complex128 for any K.  No atomics, no barrier across workgroups.  Beyond the G gathered reads of T_{k-1} an order moves one read
+ *   of T_{k-1}[b] and T_{k-2}[b], one write of T_k[b], one read and one write of out[b]: 16 (G + 4) bytes per row and order beyond the
+ *   cached re-read.  *form (may be NULL) = SYMGPU_CHEB_DIRECT; it is the only form (a plan without terms still runs the kernels, with
+ *   h = 0).  The device memory is checked before it is allocated (SYMGPU_E_NOMEM); the scratch is freed before the call returns, also
+ *   on failure. */
+#define SYMGPU_CHEB_DIRECT 1
+int symgpu_cheb_apply(struct symgpu_matvec_s *plan, double centre, double half_width, const double *coef_host /* [K+1][2] (re, im) */, int64_t K,
+                      const double *psi_dev, double *out_dev, int *form /* or NULL */);
+
 /* ---- f6: PauliwordOp.from_matrix (base.py:239-425), the inverse of f5: the Pauli decomposition of a 2^n x 2^n matrix M, n_qubits 1 .. 31
  * (csrc/pauli_decomp.hip).  With the conventions of f5 (qubit 0 the MOST significant bit of b, x, z):
  *   c(x, z) = i^{|x & z| mod 4} 2^-n sum_b (-1)^{|b & z|} M[b, b ^ x]

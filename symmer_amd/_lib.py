@@ -137,6 +137,7 @@ SIGNATURES = {
     'symgpu_sample_draw': [P, c_i64, c_u64, c_i64, P, P, P, P, P],
     'symgpu_basis_change': [P, c_int, c_u64, c_u64, P],
     'symgpu_counts_signed_sums': [P, c_int, P, P, c_i64, P],
+    'symgpu_cheb_apply': [P, c_dbl, c_dbl, P, c_i64, P, P, P],
     'symgpu_comm_available': [],
     'symgpu_comm_unique_id': [P],
     'symgpu_comm_init': [P, c_int, c_int],

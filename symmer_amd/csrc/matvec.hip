@@ -12,34 +12,7 @@
 
 namespace symgpu {
 
-constexpr int MV_TILE = 256;                      // rows per workgroup (64 and 128 measured the same within 4 %)
-
-// ---- y = keep o (H x) ----------------------------------------------------------------------------------------------------------------
-struct MvTerms {
-    const u32 *tz;
-    const f64x2 *tc;
-    const u32 *gx;
-    const u32 *gstart;
-    u32 G;
-    int n;
-};
-
-__device__ __forceinline__ f64x2 mv_signed(f64x2 c, u32 b, u32 z) {
-    const long long neg = (long long)((u64)(__popc(b & z) & 1) << 63);
-    return f64x2{__longlong_as_double(__double_as_longlong(c.x) ^ neg), __longlong_as_double(__double_as_longlong(c.y) ^ neg)};
-}
-
-// D_g(b), the terms of group g added in operator order from the first one
-__device__ __forceinline__ f64x2 mv_group_sum(const MvTerms &P, u32 g, u32 b) {
-    const u32 t0 = P.gstart[g], t1 = P.gstart[g + 1];
-    f64x2 d = mv_signed(P.tc[t0], b, P.tz[t0]);
-    for (u32 t = t0 + 1; t < t1; ++t) {
-        const f64x2 v = mv_signed(P.tc[t], b, P.tz[t]);
-        d = f64x2{__dadd_rn(d.x, v.x), __dadd_rn(d.y, v.y)};
-    }
-    return d;
-}
-
+// ---- y = keep o (H x): MvTerms, mv_signed and mv_group_sum are in matvec.h, shared with evolve.hip -------------------------------------
 __global__ __launch_bounds__(MV_TILE) void k_mv_apply(MvTerms P, const f64x2 *__restrict__ x, f64x2 *__restrict__ y, const uint8_t *__restrict__ keep) {
     const u64 rows = (u64)1 << P.n;
     const u64 b64 = (u64)blockIdx.x * MV_TILE + threadIdx.x;
@@ -74,11 +47,6 @@ __global__ __launch_bounds__(256) void k_mv_sector(MvTerms P, long long n_partic
     }
     __syncthreads();
     if (threadIdx.x == 0 && s_cnt) atomicAdd(n_kept, (unsigned long long)s_cnt);
-}
-
-static MvTerms mv_terms_of(const symgpu_matvec_s *p) {
-    const XGroups &g = p->xg;
-    return MvTerms{g.tz.as<u32>(), g.tc.as<f64x2>(), g.gx.as<u32>(), g.gstart.as<u32>(), g.G, g.n};
 }
 
 int matvec_require_memory(u64 bytes, const char *what) {

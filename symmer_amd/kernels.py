@@ -699,6 +699,7 @@ def to_csr(devop, n_qubits, index_dtype=None):
 
 # ---- H x on dense statevectors and the vector kernels of exact_gs_energy (csrc/matvec.hip, csrc/lanczos.hip) --------------------------
 MATVEC_DIRECT = 1                            # SYMGPU_MATVEC_DIRECT: the form a matvec_apply reports (0: no kernel ran, T = 0)
+CHEB_DIRECT = 1                              # SYMGPU_CHEB_DIRECT: the form a cheb_apply reports, the only one
 
 
 class DeviceBuffer:
@@ -803,6 +804,20 @@ class MatvecPlan:
             raise MemoryError(_lib.last_error())
         check(rc)
         return alpha.value, beta.value
+
+    def chebyshev(self, centre, half_width, coeffs, psi, out):
+        """``out = sum_k coeffs[k] T_k((H - centre) / half_width) psi`` for two ``DeviceBuffer`` of ``2^n`` complex128 (not the same
+        one; ``psi`` is not written) and ``K + 1 >= 1`` complex coefficients: one launch per order (csrc/evolve.hip), in the arithmetic
+        of include/symgpu.h f11.  The spectrum of ``H`` must lie in ``[centre - half_width, centre + half_width]``.  Returns the form
+        that ran (``CHEB_DIRECT``)."""
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.complex128).reshape(-1)
+        form = c_int(0)
+        rc = _lib.lib().symgpu_cheb_apply(self.handle, float(centre), float(half_width), addr(coeffs), coeffs.shape[0] - 1,
+                                          None if psi is None else psi.ptr, None if out is None else out.ptr, ctypes.addressof(form))
+        if rc == _lib.E_NOMEM:
+            raise MemoryError(_lib.last_error())
+        check(rc)
+        return form.value
 
     def free(self):
         if self.handle is not None and self.handle.value:
