@@ -751,6 +751,27 @@ int symgpu_noncon_signs_dev(symgpu_op_t terms, symgpu_op_t gens, const uint64_t 
 int symgpu_noncon_search(const double *coeff, const uint64_t *mask, const int32_t *clique, int64_t T, int n_free, int64_t n_cliques,
                          double *best_energy, uint64_t *best_mask, double *energies /* [2^n_free] or NULL */, int64_t *info /* [4] or NULL */);
 
+/* ---- h2: noncontextual sweeps (utils.py:592-616 perform_noncontextual_sweep; noncontextual_op.py:126-226 the three constructors on it;
+ * csrc/noncon_sweep.hip) ----------------------------------------------------------------------------------------------------------------
+ * symgpu_noncon_sweep_dev   n_starts sweeps over the T terms of op.  Sweep s visits the terms order[(starts[s] + i) % T], i = 0 .. T-1, and
+ *   keeps a term whenever the kept terms stay noncontextual (the first visited term is always kept).  order: a host permutation of
+ *   0 .. T-1, NULL = the identity; starts: host [n_starts], each in [0, T).  Coefficients are not read.
+ *   kept_bits: host [n_starts][ceil(T/64)]; bit p % 64 of word p / 64 of row s is set iff the term at POSITION p of order (not of the
+ *   rolled visit) was kept by sweep s; the bits at or above T are zero.
+ *   labels (may be NULL): host int32 [n_starts][T] by position: -2 rejected, -1 kept and commuting with every kept term, c >= 0 kept in
+ *   the clique numbered c in order of creation (two kept terms with labels >= 0 commute iff their labels are equal).
+ *   info (may be NULL) int64 [4]: [0] bytes of the commutation table, [1] workgroups launched, [2] sweeps a workgroup ran at most,
+ *   ceil(n_starts / [1]), [3] the largest clique count a sweep ended with.  All zero when nothing was launched.
+ *   The T x T commutation bits are computed once, on the rows permuted into order (a roll is an offset into that table); one workgroup
+ *   runs one sweep, a persistent grid strides over the sweeps.  The output is integers: equal inputs give identical bytes, and a batch
+ *   gives what its sweeps give one call each.  T = 0, T = 1 and n_starts = 0 return without a launch (T = 1: the term is kept, label -1).
+ *   SYMGPU_E_INVALID, before anything is allocated: a null handle; T above SYMGPU_NONCON_SWEEP_MAX_T (the table takes T^2 / 8 bytes, 2 GiB
+ *   at the cap, and the three masks of a sweep 3 T / 8 bytes of LDS, 48 KiB at the cap); n_starts < 0; a start outside [0, T); an order
+ *   that is not a permutation; null starts or kept_bits with sweeps to run.  Scratch is freed before the call returns, also on failure. */
+#define SYMGPU_NONCON_SWEEP_MAX_T 131072
+int symgpu_noncon_sweep_dev(symgpu_op_t op, const int64_t *order /* [T] or NULL */, int64_t n_starts, const int64_t *starts /* [n_starts] */,
+                            uint64_t *kept_bits /* [n_starts][ceil(T/64)] */, int32_t *labels /* [n_starts][T] or NULL */, int64_t *info /* [4] or NULL */);
+
 /* ---- e: multi-GPU (one process per GPU; RCCL over xGMI) ------------------------------------------- */
 #define SYMGPU_UNIQUE_ID_BYTES 128
 int symgpu_comm_available(void);                                                /* librccl loadable? (no device, no collective) */

@@ -112,6 +112,7 @@ SIGNATURES = {
     'symgpu_clique_colour_dev': [P, c_int, P, P, P, P],
     'symgpu_noncon_signs_dev': [P, P, P, c_int, P],
     'symgpu_noncon_search': [P, P, P, c_i64, c_int, c_i64, P, P, P, P],
+    'symgpu_noncon_sweep_dev': [P, P, c_i64, P, P, P, P],
     'symgpu_to_csr_count': [P, c_int, P, P, PP],
     'symgpu_to_csr_fill': [P, P, P, P, c_int],
     'symgpu_from_matrix_dense': [P, c_int, P, P, c_i64, PP, P, P, P],

@@ -333,6 +333,42 @@ def noncon_search(coeff, masks, clique, n_free, n_cliques, want_energies=False, 
     return out
 
 
+# ---- noncontextual sweeps (csrc/noncon_sweep.hip) -------------------------------------------------------------------------------------
+NONCON_SWEEP_MAX_T = 131072                  # SYMGPU_NONCON_SWEEP_MAX_T: symgpu_noncon_sweep_dev refuses more terms (a 2 GiB table)
+SWEEP_REJECTED, SWEEP_SYM = -2, -1           # labels of a sweep; >= 0: the clique, numbered in order of creation
+
+
+def noncon_sweep(op, order=None, starts=None, want_labels=False, want_info=False):
+    """Noncontextual sweeps over the terms of a device operator (``symgpu_noncon_sweep_dev``): sweep ``s`` visits the terms
+    ``order[(starts[s] + i) % T]``, i = 0 .. T-1, and keeps a term whenever the kept terms stay noncontextual.  ``order``: a permutation
+    of the term indices (default: as they stand); ``starts``: the roll offsets (default: one sweep from position 0).  Returns
+    bool[n_starts, T], True where the term at POSITION p of ``order`` was kept; then, with ``want_labels``, int32[n_starts, T] by position
+    (``SWEEP_REJECTED``, ``SWEEP_SYM``, or the clique); then, with ``want_info``, the call's info words (table bytes, workgroups, sweeps
+    a workgroup, largest clique count).  All sweeps of a call share one commutation table and run as one launch."""
+    t = op.n_terms
+    if t > NONCON_SWEEP_MAX_T:
+        raise ValueError(f'{t} terms: a sweep takes at most {NONCON_SWEEP_MAX_T} (the commutation table takes T^2 / 8 bytes)')
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        if order.shape != (t,) or not np.array_equal(np.sort(order), np.arange(t)):
+            raise ValueError('order must be a permutation of the term indices')
+    starts = np.zeros(1, dtype=np.int64) if starts is None else np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+    if t > 0 and starts.size and (starts.min() < 0 or starts.max() >= t):
+        raise ValueError(f'every start must lie in [0, {t})')
+    n_starts, words = starts.shape[0], (t + 63) // 64
+    bits = np.zeros((n_starts, words), dtype='<u8')
+    labels = np.full((n_starts, t), SWEEP_REJECTED, dtype=np.int32) if want_labels else None
+    info = np.zeros(4, dtype=np.int64)
+    check(_lib.lib().symgpu_noncon_sweep_dev(op.handle, addr(order), n_starts, addr(starts), addr(bits), addr(labels), addr(info)))
+    kept = np.unpackbits(bits.view(np.uint8).reshape(n_starts, words * 8), axis=1, bitorder='little')[:, :t].astype(bool)
+    out = (kept,)
+    if want_labels:
+        out += (labels,)
+    if want_info:
+        out += (info,)
+    return out if len(out) > 1 else kept
+
+
 def mul_allpairs(inner, ci, outer, co, inner_is_left=True):
     """Uncleaned product: row ``o*Ni + i`` = ``inner[i] ^ outer[o]`` with its phase-corrected coefficient."""
     inner, outer, ci, co = _rows(inner), _rows(outer), _coeff(ci), _coeff(co)

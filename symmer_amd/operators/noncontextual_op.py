@@ -13,7 +13,12 @@ the reference evaluates ``get_energy`` once per assignment in a process pool.
 Out of scope: ``AntiCommutingOp`` and ``unitary_partitioning`` do not exist here, so ``clique_operator`` is a plain ``PauliwordOp``
 whose coefficients after ``solve`` are the clique sums s_i themselves (the reference normalises them and keeps ``mapped_clique_rep``,
 ``unitary_partitioning_rotations`` and ``clique_normalization``), and ``noncon_state`` raises ``NotImplementedError``.  Also not built:
-``draw_graph_structure``, ``random``, and the ``stabilizers`` / ``DFS_*`` / ``SingleSweep_*`` strategies of ``from_hamiltonian``.
+``draw_graph_structure``, ``random``, and the ``stabilizers`` strategy of ``from_hamiltonian``.
+
+The sweeping constructors — ``_single_sweep_noncontextual_operator``, ``_dfs_noncontextual_op``, ``_diag_first_noncontextual_op`` — are
+built on one device call per constructor (``symgpu_noncon_sweep_dev``, ``csrc/noncon_sweep.hip``, DESIGN.md §3.20: one commutation table,
+one workgroup per sweep, all rolls of the DFS form in one launch); their public door is ``NoncontextualOp.from_sweep``, which parses
+``SingleSweep_*``, ``DFS_*`` and ``diag_first``.  ``from_hamiltonian`` itself still refuses ``DFS_*`` and ``SingleSweep_*``.
 """
 import warnings
 from typing import Tuple
@@ -63,6 +68,82 @@ class NoncontextualOp(PauliwordOp):
         """noncontextual_op.py:108-124: the diagonal terms, the simplest noncontextual operator."""
         mask_diag = np.where(~np.any(H.X_block, axis=1))
         return cls(H.symp_matrix[mask_diag], H.coeff_vec[mask_diag])
+
+    # ---- constructors by sweeping (csrc/noncon_sweep.hip, DESIGN.md §3.20) ------------------------------------------------
+    @classmethod
+    def from_sweep(cls, H: PauliwordOp, strategy: str = 'SingleSweep_magnitude', max_rolls: int = None) -> "NoncontextualOp":
+        """The sweeping strategies of the reference's ``from_hamiltonian`` (noncontextual_op.py:99-104) and its ``_diag_first``
+        constructor: ``'SingleSweep_magnitude' | 'SingleSweep_random' | 'SingleSweep_CurrentOrder'``, ``'DFS_magnitude' | 'DFS_largest'``
+        (``max_rolls``: the first rolls only) and ``'diag_first'``."""
+        if strategy == 'diag_first':
+            return cls._diag_first_noncontextual_op(H)
+        if strategy.find('DFS') != -1:
+            _, strategy = strategy.split('_')
+            return cls._dfs_noncontextual_op(H, strategy=strategy, max_rolls=max_rolls)
+        if strategy.find('SingleSweep') != -1:
+            _, strategy = strategy.split('_')
+            return cls._single_sweep_noncontextual_operator(H, strategy=strategy)
+        raise ValueError(f'Unrecognised noncontextual operator strategy {strategy}')
+
+    @classmethod
+    def _swept(cls, H: PauliwordOp, order: np.ndarray, starts=None) -> np.ndarray:
+        """bool[n_starts, T]: the positions of ``order`` that the sweeps from ``starts`` keep, all sweeps in one device call."""
+        if H.n_terms == 0:
+            return np.zeros((1 if starts is None else len(starts), 0), dtype=bool)
+        return kernels.noncon_sweep(H._device(rows_only=True), order=order, starts=starts)
+
+    @classmethod
+    def _single_sweep_noncontextual_operator(cls, H: PauliwordOp, strategy: str = 'magnitude') -> "NoncontextualOp":
+        """noncontextual_op.py:193-226: order the terms by ``'magnitude'``, at ``'random'`` (``np.random.shuffle`` on the host, as the
+        reference: seeding ``np.random`` reproduces its order) or leave them in their ``'CurrentOrder'``, and sweep once."""
+        if strategy == 'magnitude':
+            order = PauliwordOp._ORDERINGS['magnitude'](H)
+        elif strategy == 'random':
+            order = np.arange(H.n_terms)
+            np.random.shuffle(order)
+        elif strategy == 'CurrentOrder':
+            order = np.arange(H.n_terms)
+        else:
+            raise ValueError('Unrecognised strategy, must be one of magnitude, random or CurrentOrder')
+        kept = cls._swept(H, order)[0]
+        return cls.from_PauliwordOp(H[order[np.flatnonzero(kept)]])
+
+    @classmethod
+    def _dfs_noncontextual_op(cls, H: PauliwordOp, runtime=10, strategy: str = 'magnitude', max_rolls: int = None) -> "NoncontextualOp":
+        """noncontextual_op.py:126-169: one sweep per cyclic roll of the magnitude order, the best one kept — by the sum of the kept
+        magnitudes (``'magnitude'``) or by the number of kept terms (``'largest'``); the first roll among equal scores wins, as in the
+        reference's stable sort.  Every roll 0 .. T-1 runs, all of them in ONE device call on one commutation table; ``max_rolls`` runs
+        the first ``max_rolls`` rolls only.  ``runtime`` is unused: the reference stops after that many seconds of wall clock, which
+        is not reproducible, and the whole pass is affordable here."""
+        if strategy not in ('magnitude', 'largest'):
+            raise ValueError('Unrecognised noncontextual operator strategy.')
+        T = H.n_terms
+        order = PauliwordOp._ORDERINGS['magnitude'](H)
+        if T == 0:
+            return cls.from_PauliwordOp(H)
+        if max_rolls is not None and max_rolls < 1:
+            raise ValueError('max_rolls must be at least 1')
+        n_rolls = T if max_rolls is None else min(int(max_rolls), T)
+        kept = cls._swept(H, order, starts=np.arange(n_rolls))
+        magnitudes = abs(H._c()[order])
+        best, best_score, best_visit = -1, None, None
+        for n in range(n_rolls):
+            visit = np.roll(np.arange(T), -n)
+            visit = visit[kept[n, visit]]                               # the kept positions in the order this roll visited them
+            score = -np.sum(magnitudes[visit]) if strategy == 'magnitude' else -len(visit)
+            if best < 0 or score < best_score:
+                best, best_score, best_visit = n, score, visit
+        return cls.from_PauliwordOp(H[order[best_visit]])
+
+    @classmethod
+    def _diag_first_noncontextual_op(cls, H: PauliwordOp) -> "NoncontextualOp":
+        """noncontextual_op.py:171-191: the diagonal terms (they commute with each other: all are kept), then the off-diagonal terms by
+        decreasing magnitude, each kept if the operator stays noncontextual — one sweep over that order."""
+        diagonal = ~np.any(H.X_block, axis=1)
+        off = np.flatnonzero(~diagonal)
+        order = np.concatenate([np.flatnonzero(diagonal), off[np.argsort(-abs(H._c()[off]))]]).astype(np.int64)
+        kept = cls._swept(H, order)[0]
+        return cls.from_PauliwordOp(H[order[np.flatnonzero(kept)]])
 
     @classmethod
     def _from_generators_noncontextual_op(cls, H: PauliwordOp, generators: PauliwordOp, use_jordan_product: bool = False

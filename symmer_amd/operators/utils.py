@@ -133,6 +133,16 @@ def check_adjmat_noncontextual(adjmat) -> bool:
     return bool(np.all(np.count_nonzero(unique_character, axis=0) == 1))
 
 
+def perform_noncontextual_sweep(operator) -> "PauliwordOp":
+    """Reference utils.py:592-616: one sweep over the terms in their order, keeping a term whenever the kept terms stay noncontextual.
+    One device call (csrc/noncon_sweep.hip) where the reference pads an adjacency matrix and takes its unique rows once per term.  An
+    operator without terms comes back as it is: there is nothing to keep."""
+    if operator.n_terms == 0:
+        return operator
+    kept = kernels.noncon_sweep(operator._device(rows_only=True))[0]
+    return operator[np.flatnonzero(kept)]
+
+
 def check_jordan_independent(operators) -> bool:
     """Reference utils.py:521-566: independence under the Jordan product PQ = {P,Q}/2.  At most 3n terms; the globally
     commuting terms must be independent as ordinary generators; then the rows [X-only | Z-only | Y] (Y treated as its own
